@@ -11,14 +11,17 @@ Inputs (dictionary and signals) are resident in HBM before the timed region star
 on the device and, with N > 1 ranks, are exchanged by ONE all_gather (RCCL) inside the timed
 region.  Signals are independent: weak scaling, K signals per rank.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).  At N = 1 the line also
-carries, under "secondary", the results of the other single-GPU configurations of BASELINE.json measured
-by the same process right after the headline: configs[2] (batched, bf16 MFMA screen) and configs[4] (GOMP
-S = 4 and Subspace Pursuit on 8192 x 131072, k = 512) -- each with its own roofline block.  The headline
-stays configs[1]; --no-secondary skips them.
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).  A plain run sets up, warms
+up, times the K steps and prints the headline.  --dump-outputs DIR writes what the last timed step returned
+(DIR/*.npy, float64).  --full adds everything else the bench measures and checks: at N = 1 the CPU baseline
+and, under "secondary", the other single-GPU configurations of BASELINE.json measured by the same process
+right after the headline: configs[2] (batched, bf16 MFMA screen) and configs[4] (GOMP S = 4 and Subspace
+Pursuit on 8192 x 131072, k = 512) -- each with its own roofline block; at N > 1 the recomputation check of
+the gathered rows; and the detail file (DETAIL_FILE).  The headline stays configs[1]; --no-cpu-baseline and
+--no-secondary skip parts of --full.
 """
 import argparse
 import json
@@ -35,6 +38,14 @@ M, N, K_ATOMS = 4096, 65536, 256
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured float4 copy)
 NOISE = 5e-3  # ||e||_2, as test/matchingpursuit.jl:12-13 (perturb(b, delta/2), delta = 1e-2)
 SEED_A = 0xC0FFEE
+
+
+def dump_outputs(folder, arrays):
+    """--dump-outputs: every array as folder/<name>.npy in float64 (atom indices are exact there)."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(folder, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def free_port():
@@ -161,22 +172,27 @@ def headline(out):
     return line
 
 
-def emit(out):
-    """Detail to DETAIL_FILE in the cwd (best effort), then the compact headline as the last stdout line."""
-    try:
-        with open(DETAIL_FILE, "w") as f:
-            json.dump(out, f, indent=1)
-        out = dict(out, secondary_file=DETAIL_FILE)
-    except OSError:
-        pass
+def emit(out, detail=True):
+    """Detail to DETAIL_FILE in the cwd (best effort; --full runs only), then the compact headline as the last stdout line."""
+    if detail:
+        try:
+            with open(DETAIL_FILE, "w") as f:
+                json.dump(out, f, indent=1)
+            out = dict(out, secondary_file=DETAIL_FILE)
+        except OSError:
+            pass
     print(headline(out), flush=True)
 
 
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=18)
-    p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--steps", type=int, default=None, help="timed steps (default: 18, or the workload's own count)")
+    p.add_argument("--warmup", type=int, default=None, help="warm-up steps (default: 3, or the workload's own count)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: the CPU baseline, the secondary workloads, the N > 1 gather check and the detail file")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="write what the last timed step returned to DIR/*.npy (float64; the default workload)")
     p.add_argument("--batch-cert", choices=["statistical", "rigorous"], default="rigorous", help="--workload batched: CSMP_OPT_BATCH_CERT (rigorous is the library's default)")
     p.add_argument("--batch-gram", action="store_true", help="--workload batched: CSMP_OPT_BATCH_GRAM (resident G = A'A, 32 GiB)")
     p.add_argument("--no-in-flight", action="store_true", help="--workload ompr / srr: skip the three-solves-in-flight part (a kernel trace of the one-solve-at-a-time loop alone)")
@@ -190,14 +206,26 @@ def parse():
                         "exchange runs over gloo through host memory (RCCL refuses two ranks on one device) -- exercises every line of the "
                         "multi-rank code; the numbers are NOT a scaling measurement")
     p.add_argument("--in-flight", type=int, default=0, help="--workload sp: CSMP_OPT_SOLVES_IN_FLIGHT (1..4; 0 = the library's default)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline of --full")
     p.add_argument("--batch-screen", choices=["f16", "bf16", "int8"], default="f16", help="--workload batched: CSMP_OPT_BATCH_SCREEN (operands of the screening GEMM; int8 needs --batch-cert statistical)")
     p.add_argument("--screened", action="store_true", help="--workload gomp / gomp_single / sp / sp_single: CSMP_OPT_SCREENED_SWEEP (image sweeps, certified selections)")
     p.add_argument("--screen-image", choices=["f16", "bf16", "int8"], default="f16", help="--workload screened, --screened: the image the sweeps read (CSMP_OPT_SCREENED_SWEEP = 3 / 1 / 2)")
-    p.add_argument("--no-secondary", action="store_true", help="skip the configs[2] / configs[4] blocks of the default line")
+    p.add_argument("--no-secondary", action="store_true", help="skip the configs[2] / configs[4] blocks of --full")
     p.add_argument("--profile-every", type=int, default=8, help="time every n-th sweep launch with HIP events (1 = all)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline sample")
-    return p.parse_args()
+    a = p.parse_args()
+    # the workloads' own step counts, taken when neither --steps nor --warmup is given (a missing one of the two is 18 / 3)
+    own = {"gomp": (9, 3), "sp": (9, 3), "fr": (9, 3), "screened": (9, 3), "ompr": (6, 1), "srr": (6, 1),
+           "gomp_single": (3, 1), "sp_single": (3, 1), "batched": (3, 1), "colsharded": (3, 1)}
+    if a.steps is None and a.warmup is None:
+        a.steps, a.warmup = own.get(a.workload, (18, 3))
+    a.steps = 18 if a.steps is None else a.steps
+    a.warmup = 3 if a.warmup is None else a.warmup
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.workload != "omp":
+        p.error("--dump-outputs writes the default workload's outputs (--workload omp)")
+    return a
 
 
 def make_dictionary(torch, dev):
@@ -853,7 +881,7 @@ def run_twostage(args, cs, torch, dev, At, D, show=True):
         out["three_in_flight"] = {"solves": len(many), "ms_per_solve": dt3 / len(many) * 1e3, "solves_per_s": len(many) / dt3,
                                   "iterations_equal_single": bool(sum(its[:K]) == iters)}
     if show:
-        emit(out)
+        emit(out, detail=args.full)
     return out
 
 
@@ -897,7 +925,7 @@ def run_fr(args, cs, torch, dev, At, D, show=True):
                         "launch_duration_us": duration * 1e6, "launches_in_flight": 2 if two else 1}}
     D.ctx.profile_enable(False)
     if show:
-        emit(out)
+        emit(out, detail=args.full)
     return out
 
 
@@ -935,7 +963,7 @@ def run_colsharded(args, cs, torch, dist, dev, rank, world, use_dist, ranks_seen
     several GPUs speed up a single omp(A, b, k) (src/matchingpursuit.jl:73-82).  Every rank holds N / world columns and a
     replica of the solver state; one all_gather of one 16-KiB record per rank and step (sharded.omp_colsharded)."""
     import numpy as np
-    K, W = (args.steps, args.warmup) if (args.steps, args.warmup) != (18, 3) else (3, 1)
+    K, W = args.steps, args.warmup
     At = make_dictionary(torch, dev)
     B = make_signals(torch, dev, At, 0, K + W)  # the SAME signals on every rank
     sigs = [B[s].cpu().numpy() for s in range(K + W)]
@@ -989,7 +1017,7 @@ def run_colsharded(args, cs, torch, dist, dev, rank, world, use_dist, ranks_seen
             out["equals_unsharded_omp"] = bool(np.array_equal(ref[0], res["first"][0]) and np.array_equal(ref[2], res["first"][2]))
         if not res["ranks_agree_on_first_support"] or res["supports_gathered"] != world:
             out["error"] = "ranks disagree on the support of the first timed signal"
-        emit(out)
+        emit(out, detail=args.full)
     D.close()
     return out
 
@@ -1078,8 +1106,6 @@ def main():
             sys.exit(3)
         return
     if args.workload in ("gomp", "sp", "gomp_single", "sp_single"):
-        if args.steps == 18 and args.warmup == 3:
-            args.steps, args.warmup = (9, 3) if args.workload in ("gomp", "sp") else (3, 1)
         if rank == 0:
             At5, D5 = make_dictionary5(cs, torch, dev)
             for kv in filter(None, args.tune.split(",")):
@@ -1087,50 +1113,44 @@ def main():
             if args.in_flight:
                 D5.ctx.set_option("solves_in_flight", args.in_flight)
             emit(measure_config5(args.workload, args.steps, args.warmup, cs, torch, dev, D5, At5,
-                                 screened={"f16": 3, "bf16": 1, "int8": 2}[args.screen_image] if args.screened else 0))
+                                 screened={"f16": 3, "bf16": 1, "int8": 2}[args.screen_image] if args.screened else 0), detail=args.full)
             D5.close()
         return finish()
     if args.workload == "shapes":
         if rank == 0:
-            emit(run_shapes(args, cs, torch, np, dev))
+            emit(run_shapes(args, cs, torch, np, dev), detail=args.full)
         return finish()
     At = make_dictionary(torch, dev)
     D = cs.Dictionary(At, device=local)  # borrowed, zero-copy
     for kv in filter(None, args.tune.split(",")):
         D.ctx.tune(kv.split("=")[0], int(kv.split("=")[1]))
     if args.workload in ("fr", "ompr", "srr"):
-        if args.steps == 18 and args.warmup == 3:
-            args.steps, args.warmup = (9, 3) if args.workload == "fr" else (6, 1)
         if rank == 0:
             (run_fr if args.workload == "fr" else run_twostage)(args, cs, torch, dev, At, D)
         D.close()
         return finish()
     if args.workload == "screened":
-        if args.steps == 18 and args.warmup == 3:
-            args.steps, args.warmup = 9, 3
         if rank == 0:
             emit(measure_screened_omp(args.steps, args.warmup, torch, dev, At, D, D.eps,
-                                      cert=1 if args.batch_cert == "rigorous" else 0, image={"f16": 3, "bf16": 1, "int8": 2}[args.screen_image]))
+                                      cert=1 if args.batch_cert == "rigorous" else 0, image={"f16": 3, "bf16": 1, "int8": 2}[args.screen_image]), detail=args.full)
         D.close()
         return finish()
     if args.workload == "streamed":
         if rank == 0:
             Bs = make_signals(torch, dev, At, 0, 4)
-            out = measure_streamed_omp(cs, torch, dev, At, D, Bs, D.eps, solves=3 if args.steps == 18 else max(1, min(args.steps, 3)))
+            out = measure_streamed_omp(cs, torch, dev, At, D, Bs, D.eps, solves=min(args.steps, 3))
             out.update({"n_gpus": 1, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                         "ms_per_step": out["ms_per_solve"], "config": {"workload": "configs[1] dictionary (4096x65536 Float32, 1 GiB) in host memory, k=16"}})
-            emit(out)
+            emit(out, detail=args.full)
         D.close()
         return finish()
     if args.workload == "batched":
-        if args.steps == 18 and args.warmup == 3:
-            args.steps, args.warmup = 3, 1
         out = measure_batched(args.steps, args.warmup, cs, torch, dist, dev, rank, world, At, D, use_dist,
                               cert=1 if args.batch_cert == "rigorous" else 0, gram=1 if args.batch_gram else 0,
                               screen={"f16": 3, "bf16": 0, "int8": 1}[args.batch_screen])
         if rank == 0:
             out["ranks_seen"], out["devices"] = ranks_seen, devices
-            emit(out)
+            emit(out, detail=args.full)
         D.close()
         return finish()
     eps = D.eps  # eps(Float32): omp(A, b, k) default (src/matchingpursuit.jl:85)
@@ -1184,6 +1204,9 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(atoms, op=dist.ReduceOp.SUM)
     tmax, atoms = tmax.item(), atoms.item()
+    if args.dump_outputs and rank == 0:  # what a caller of csmp_omp_batch received for the last timed signal
+        s = W + K - 1
+        dump_outputs(args.dump_outputs, {"idx": idx[s].cpu().numpy(), "val": val[s].cpu().numpy(), "nnz": nnz[s:s + 1].cpu().numpy()})
 
     if rank == 0:
         alg_bytes = M * N * 4  # bytes/atom = M*N*sizeof(Float32), A streamed once
@@ -1224,7 +1247,7 @@ def main():
                           "rocprofv3 row's AverageNs is THIS number)" % (args.profile_every, window["launches"], bracket_ms * 1e3)) if two else
                          ("HIP events on the library's stream around every %d-th steady-state tick of the timed region, minus the reading of "
                           "an empty event pair (%.2f us)" % (args.profile_every, bracket_ms * 1e3)), "event_pair_us": bracket_ms * 1e3}
-        rp = rocprof_row(tick_kernel_name(D), pattern="r06_bench_kernel_stats.csv")
+        rp = rocprof_row(tick_kernel_name(D), pattern="r06_bench_kernel_stats.csv") if args.full else None
         if rp:
             roof["committed_profile"] = rp
         out = {
@@ -1242,7 +1265,7 @@ def main():
             "roofline": roof,
             "atoms_selected": int(atoms),
         }
-        if use_dist:
+        if use_dist and args.full:
             # the one exchange, checked: a row for every signal of every rank, and the first timed signal of every rank
             # recomputed HERE (rank 0 regenerates it from its global id) must be the gathered row
             gi, gv, gn = cs.unpack_t(gathered, K_ATOMS)
@@ -1257,14 +1280,14 @@ def main():
                                    "first_signal_of_every_rank_equals_rank0_recomputation": ok}
             if int(gathered.shape[0]) != world * K or not all(ok):
                 out["error"] = "gathered results do not match: see gather_check"
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg runs on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg runs on rank 0 at N = 1 only
             try:
                 # selection order of signal W (first timed signal) for the parity cross-check
                 i0, v0, o0 = D.ctx.omp(B[W].cpu().numpy(), K_ATOMS, eps)
                 out["cpu_baseline"] = cpu_baseline(At, B[W:], o0, args.cpu_seconds)
             except Exception as e:  # noqa: BLE001
                 out["cpu_baseline"] = {"value": None, "error": repr(e)}
-        if not args.no_secondary and world == 1:
+        if args.full and not args.no_secondary and world == 1:
             # the other single-GPU configurations of BASELINE.json, measured by this same process (builder-run lines
             # of them also sit under profiles/; these are the driver-run ones)
             sec = {}
@@ -1329,7 +1352,7 @@ def main():
                                                              "equals_exact_path": sc["batch"]["equals_exact_path"], "fallbacks": sc["batch"]["stats"]["fallbacks"]}
             except Exception:  # noqa: BLE001
                 pass
-        emit(out)
+        emit(out, detail=args.full)
     D.close()
     finish()
 

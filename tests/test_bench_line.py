@@ -81,3 +81,28 @@ def test_headline_carries_both_ceilings_of_the_batched_step_and_the_device_resid
     assert all(v is None or isinstance(v, (int, float)) for v in o["secondary"].values())
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "profile_overhead" in src and "statistical_int8" not in src.split("def main()")[1].split("for name, cert, gram, scr in")[1][:400]
+
+
+def test_step_counts_options_and_dump_format(tmp_path, monkeypatch):
+    """--steps / --warmup are the timed and warm-up counts whenever given (a workload's own counts only when neither is); --full is
+    off by default; --dump-outputs writes float64 .npy files, for the default workload only."""
+    import numpy as np
+    import pytest
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.parse()
+    a = parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (18, 3, False, "")
+    assert (parse("--workload", "batched").steps, parse("--workload", "batched").warmup) == (3, 1)
+    for wl in ("omp", "batched", "gomp", "fr", "colsharded"):
+        b = parse("--workload", wl, "--steps", "18", "--warmup", "3")
+        assert (b.steps, b.warmup) == (18, 3), wl
+    assert (parse("--steps", "5").steps, parse("--steps", "5").warmup) == (5, 3)
+    assert parse("--full", "--dump-outputs", str(tmp_path)).full
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--workload", "fr", "--dump-outputs", str(tmp_path)]):
+        with pytest.raises(SystemExit):
+            parse(*bad)
+    bench.dump_outputs(str(tmp_path / "d"), {"idx": np.array([3, 2**40], np.int64), "val": np.ones(2, np.float32)})
+    idx, val = np.load(tmp_path / "d" / "idx.npy"), np.load(tmp_path / "d" / "val.npy")
+    assert idx.dtype == val.dtype == np.float64 and idx.tolist() == [3, 2**40] and val.tolist() == [1.0, 1.0]

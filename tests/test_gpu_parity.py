@@ -1907,7 +1907,7 @@ def test_column_sharded_omp_ties_and_stops(cs, oracle):
 def test_bench_two_ranks_rehearsal_on_one_gpu(workload, tmp_path):
     """The N > 1 code of bench.py end to end on the GPU box: two ranks under torchrun sharing the one GPU (--share-gpu: the
     exchange over gloo, because RCCL refuses two ranks on one device).  Checks the JSON contract of the multi-rank line (the compact
-    headline on stdout, the detail in bench_secondary.json): ranks seen, the gathered rows and the recomputation check of the
+    headline on stdout, the detail in bench_secondary.json; both --full): ranks seen, the gathered rows and the recomputation check of the
     signal-sharded workload, the cross-rank agreement of the column-sharded one.  omp_rccl_world1: ONE rank under the launcher
     with the "nccl" backend -- the path the driver's N > 1 runs take, with the collective inside the library (csmp_omp_sharded).
     Not a scaling measurement."""
@@ -1927,7 +1927,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(workload, tmp_path):
              "batched8": ["--workload", "batched", "--steps", "1", "--warmup", "0"]}[workload]
     share = [] if workload == "omp_rccl_world1" else ["--share-gpu"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world)] + share + extra
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full"] + share + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-2000:]
     last = out.stdout.strip().splitlines()[-1]
@@ -1945,6 +1945,39 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(workload, tmp_path):
         assert line["ranks_agree_on_first_support"] and detail["supports_gathered"] == 2 and line["scaling"] == "strong"
     else:
         assert line["matches_exact_path_on_sample"] and abs(line["value"] * line["ms_per_step"] * 1e-3 - world * 1024 * 128) < 5.0
+
+
+def test_bench_plain_run_and_dumped_outputs(cs, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps and prints the headline only (no CPU baseline, no secondary
+    workloads, no detail file); --dump-outputs writes what the last timed step returned, and that is a lone omp call's result on
+    the same signal (signal W + K - 1 of rank 0)."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    import bench
+    K, W = 2, 1
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                          "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == K and line["warmup"] == W and line["ms_per_step"] > 0 and line["unit"] == "atoms/s"
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 256) < 1.0  # (every solve selects k = 256 atoms here)
+    assert "cpu_baseline" not in line and "secondary" not in line and not (tmp_path / bench.DETAIL_FILE).exists()
+    got = {n: np.load(tmp_path / "dump" / (n + ".npy")) for n in ("idx", "val", "nnz")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    dev = torch.device("cuda", 0)
+    At = bench.make_dictionary(torch, dev)
+    b = bench.make_signals(torch, dev, At, 0, K + W)[K + W - 1].cpu().numpy()
+    d = cs.Dictionary(At, device=0)
+    try:
+        i, v, o = d.ctx.omp(b, 256, EPS32)
+    finally:
+        d.close()
+    n = int(got["nnz"][0])
+    gi, gv = got["idx"][:n], got["val"][:n]
+    pg, pr = np.argsort(gi), np.argsort(i)  # (the same support and coefficients, whichever order each call lists them in)
+    assert n == len(i) and np.array_equal(gi[pg], i[pr]) and close(gv[pg], v[pr], tight=False)
 
 
 # ------------------------------------------------------------------ screened single-signal sweep (CSMP_OPT_SCREENED_SWEEP)

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 stats() {  # stats <name> <bench args...>: headline line + csmp kernel rows of rocprofv3 --kernel-trace --stats
   local name=$1; shift
   rm -rf /tmp/prof_$name /tmp/w_$name; mkdir -p /tmp/w_$name; cd /tmp/w_$name
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python3 $R/bench.py "$@" > $OUT/${name}_stdout.txt 2> $OUT/${name}.err
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python3 $R/bench.py --full "$@" > $OUT/${name}_stdout.txt 2> $OUT/${name}.err
   local f=$(find /tmp/prof_$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && grep -E '^"Name"|csmp::|_ZN4csmp' "$f" > $OUT/${name}_kernel_stats.csv
   grep '^{' $OUT/${name}_stdout.txt | tail -1 > $OUT/${name}_line.json; rm -f $OUT/${name}_stdout.txt
@@ -22,9 +22,9 @@ pmc() {  # pmc <name> <counters> <bench args...> -> prints the output directory
   timeout 600 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d /tmp/pmc_$name -- python3 $R/bench.py "$@" > /dev/null 2> $OUT/pmc_${name}.err
   echo /tmp/pmc_$name
 }
-# the driver's command, unprofiled: the compact headline (last stdout line) and the detail file
+# the driver's command with --full, unprofiled: the compact headline (last stdout line) and the detail file
 mkdir -p /tmp/w_plain; cd /tmp/w_plain
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default_stdout.txt 2> $OUT/bench_default.err
+python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default_stdout.txt 2> $OUT/bench_default.err
 tail -1 $OUT/bench_default_stdout.txt > $OUT/bench_default_line.json; cp bench_secondary.json $OUT/bench_default_detail.json; rm -f $OUT/bench_default_stdout.txt
 cd /tmp
 stats bench --steps 18 --warmup 3 --no-cpu-baseline --no-secondary

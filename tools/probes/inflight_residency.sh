@@ -2,7 +2,7 @@
 # without the one-workgroup-per-CU LDS request (csmp_tune sweep_lds_kib).  Usage (GPU box): bash tools/probes/inflight_residency.sh
 for w in ompr srr; do
   for t in "" sweep_lds_kib=81; do
-    python bench.py --workload $w --steps 9 --warmup 1 --no-cpu-baseline ${t:+--tune $t} 2>/dev/null | tail -1 > /tmp/l.json
+    python bench.py --workload $w --steps 9 --warmup 1 --full ${t:+--tune $t} 2>/dev/null | tail -1 > /tmp/l.json
     python - "$w" "${t:-default}" <<'PY'
 import json, sys
 d = json.load(open('/tmp/l.json'))
