@@ -401,6 +401,12 @@ __device__ __forceinline__ void sweep_body_ph(
     const f64x2* rs = reinterpret_cast<const f64x2*>(lds);
     const int64_t col0 = (int64_t)bid * NW + wave, stride = (int64_t)nblk * NW;
     const int ncol = col0 < N ? (int)((N - 1 - col0) / stride + 1) : 0;  // (<= pcap: the host sized the partials for it)
+    // guard: a grid the partials were not sized for (most columns of any wave, those of wave 0 of workgroup 0, beyond pcap) would write
+    // past this wave's LDS partials -- the solve is stopped instead (STOP_FULL: the support stays what it is) and nothing is written
+    if ((N - 1) / stride + 1 > (int64_t)pcap) {
+        if (bid == 0 && tid == 0) st->done |= STOP_FULL;
+        return;
+    }
     auto units_of = [&](int ph) {  // units per column in stage ph
         const int rows_here = (Mv - ph * KP) < KP ? (Mv - ph * KP) : KP;
         return (rows_here + UR - 1) / UR;
@@ -2081,6 +2087,256 @@ __global__ __launch_bounds__(DYN ? kSweepDynThreads : kSweepThreads) void k_tick
                 sweep_body_gen<TA, U, 32 / U>(sw.A, sw.ld, sw.Mv, sw.N, sw.r, sw.cvec, sw.pval, sw.pidx, sw.st, sw.eps, sw.check_eps,
                                               sw.skipmask, bid - 2 * G, sw.nblk, sw.KP, lds);
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Shared sweep: ONE pass over the dictionary computes c = A' r for up to kGroupMax residuals (the signals of one group of the
+// grouped batch scheduler, host/omp.hpp).  The ring, the unit loads, the clamped ragged rows and the early first loads are
+// sweep_body_gen's; every A value is promoted once and multiplied into R accumulators, one per residual, each against its own LDS
+// image (r_slot layout).  Per residual the arithmetic is sweep_body_gen's alone: the same fma order per lane, the same wave_xsum,
+// ||r||^2 in the same per-thread order, its own staged c stores and its own (max |c|, first index) partials -- the same bits.
+// A member that is already stopped (st->done & skipmask) or stops on eps in this pass is masked: it writes no c and no partials.
+// The pass returns early only when every member is stopped.  dynamic LDS: R images of KP doubles + the scratch (sweep_multi_lds_bytes).
+constexpr int kGroupMax = 4;
+template <typename TA>
+struct MultiSweep {
+    const TA* A; int64_t ld; int Mv; int64_t N;
+    double eps; int check_eps, skipmask, nblk, KP;
+    int n;  // members (1 .. R; the launch's R is n)
+    const double* r[kGroupMax]; double* cvec[kGroupMax]; double* pval[kGroupMax]; int* pidx[kGroupMax]; DevState* st[kGroupMax];
+};
+inline size_t sweep_multi_lds_bytes(int KP, int R) { return ((size_t)R * KP + 16 + 32 * (size_t)R) * sizeof(double); }
+template <typename TA, int U, int NB, int R>
+__device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const int bid, double* lds) {
+    using VT = typename Vec<TA>::type;
+    constexpr int VEC = Vec<TA>::n;
+    constexpr int ROWS = kWave * VEC;
+    constexpr int UR = U * ROWS;
+    constexpr int NW = kSweepThreads / kWave;
+    static_assert((NB - 1) * U < 64, "the ring must fit the 6-bit vmcnt");
+    static_assert(R >= 1 && R <= kGroupMax, "group size");
+    unsigned live = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+        if (!(p.st[i]->done & p.skipmask)) live |= 1u << i;
+    if (!live) return;
+    const TA* __restrict__ A = p.A;
+    const int64_t ld = p.ld, N = p.N;
+    const int Mv = p.Mv, KP = p.KP, nblk = p.nblk;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nvec = Mv / VEC;
+    double* n2s = lds + (size_t)R * KP;  // [4 waves x R]
+    double* redv = n2s + 16;             // [R][4 NW]
+    int* redi = reinterpret_cast<int*>(redv + 16 * R);
+
+    const int64_t col0 = (int64_t)bid * NW + wave, stride = (int64_t)nblk * NW;
+    const int64_t ncol = col0 < N ? (N - 1 - col0) / stride + 1 : 0;
+    double bestv[R];
+    int besti[R];
+    const int nunit = (Mv + UR - 1) / UR;
+    const int Mst = nunit * UR;
+    VT buf[NB][U];
+    double cst[R], acc[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        bestv[i] = -1.0;
+        besti[i] = 0x7fffffff;
+        cst[i] = 0.0;
+        acc[i] = 0.0;
+    }
+    int64_t ccst = -1;
+    int cslot = 0;
+    int64_t icol = col0, ccol = col0;
+    int ib = 0, cb = 0;
+    const int64_t T = ncol * nunit;
+    int64_t ileft = T, cleft = T;
+    auto issue = [&](VT(&b)[U]) {
+        const VT* pc = reinterpret_cast<const VT*>(A + icol * ld);
+        const int vb = ib * (U * kWave) + lane;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int v = vb + u * kWave;
+            b[u] = __builtin_nontemporal_load(pc + (v < nvec ? v : nvec - 1));
+        }
+        if (++ib == nunit) {
+            ib = 0;
+            icol += stride;
+        }
+        --ileft;
+    };
+#pragma unroll
+    for (int d = 0; d < NB; ++d) {
+        if (ileft <= 0) {
+            icol = (ncol > 0 ? col0 + (ncol - 1) * stride : N - 1);
+            ib = 0;
+        }
+        issue(buf[d]);
+    }
+    {
+        // the images and every member's ||r||^2, each in sweep_body_gen's per-thread order
+        constexpr int RP = 16;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const double* __restrict__ r = p.r[i];
+            double* img = lds + (size_t)i * KP;
+            double n2 = 0.0;
+            for (int m0 = tid; m0 < Mst; m0 += RP * kSweepThreads) {
+                double rv[RP];
+#pragma unroll
+                for (int q = 0; q < RP; ++q) {
+                    const int m = m0 + q * kSweepThreads;
+                    rv[q] = m < Mv ? r[m] : 0.0;
+                }
+#pragma unroll
+                for (int q = 0; q < RP; ++q) {
+                    const int m = m0 + q * kSweepThreads;
+                    if (m < Mst) img[r_slot<VEC>(m)] = rv[q];
+                    n2 = fma(rv[q], rv[q], n2);
+                }
+            }
+            for (int s = 32; s >= 1; s >>= 1) n2 += __shfl_xor(n2, s, kWave);
+            if (lane == 0) n2s[wave * R + i] = n2;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            if (!(live & (1u << i))) continue;
+            const double n2 = (n2s[0 * R + i] + n2s[1 * R + i]) + (n2s[2 * R + i] + n2s[3 * R + i]);
+            if (bid == 0 && tid == 0) p.st[i]->rnorm2 = n2;
+            if (p.check_eps && !(sqrt(n2) >= p.eps)) {  // norm(residual!) >= eps || break  (:79,:132)
+                if (bid == 0 && tid == 0) p.st[i]->done |= STOP_EPS;
+                live &= ~(1u << i);
+            }
+        }
+        if (!live) return;
+    }
+    auto consume = [&](const VT(&b)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int t = cb * U + u;
+            if constexpr (VEC == 4) {
+                const double a0 = (double)b[u].x, a1 = (double)b[u].y, a2 = (double)b[u].z, a3 = (double)b[u].w;
+#pragma unroll
+                for (int i = 0; i < R; ++i) {
+                    const f64x2* rs = reinterpret_cast<const f64x2*>(lds + (size_t)i * KP);
+                    const f64x2 r01 = rs[(t * 2 + 0) * kWave + lane];
+                    const f64x2 r23 = rs[(t * 2 + 1) * kWave + lane];
+                    acc[i] = fma(a0, r01.x, acc[i]);
+                    acc[i] = fma(a1, r01.y, acc[i]);
+                    acc[i] = fma(a2, r23.x, acc[i]);
+                    acc[i] = fma(a3, r23.y, acc[i]);
+                }
+            } else {
+                const double a0 = (double)b[u].x, a1 = (double)b[u].y;
+#pragma unroll
+                for (int i = 0; i < R; ++i) {
+                    const f64x2* rs = reinterpret_cast<const f64x2*>(lds + (size_t)i * KP);
+                    const f64x2 r01 = rs[t * kWave + lane];
+                    acc[i] = fma(a0, r01.x, acc[i]);
+                    acc[i] = fma(a1, r01.y, acc[i]);
+                }
+            }
+        }
+        if (++cb == nunit) {  // the column's last unit
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                const double c = wave_xsum(acc[i]);
+                if (lane == cslot) cst[i] = c;
+                const double av = fabs(c);
+                if (av > bestv[i]) {  // columns arrive in increasing order: '>' keeps the first maximum
+                    bestv[i] = av;
+                    besti[i] = (int)ccol;
+                }
+                acc[i] = 0.0;
+            }
+            if (lane == cslot) ccst = ccol;
+            if (++cslot == kWave) {
+                if (ccst >= 0) {
+#pragma unroll
+                    for (int i = 0; i < R; ++i)
+                        if (live & (1u << i)) p.cvec[i][ccst] = cst[i];
+                }
+                ccst = -1;
+                cslot = 0;
+            }
+            cb = 0;
+            ccol += stride;
+        }
+        --cleft;
+    };
+    if (T >= 2 * NB) {
+        const int64_t groups = T / NB - 1;
+        for (int64_t g = 0; g < groups; ++g) {
+#pragma unroll
+            for (int d = 0; d < NB; ++d) {
+                consume(buf[d]);
+                issue(buf[d]);
+            }
+        }
+    }
+    while (cleft > 0) {
+#pragma unroll
+        for (int d = 0; d < NB; ++d) {
+            if (cleft == 0) break;
+            consume(buf[d]);
+            if (ileft > 0) issue(buf[d]);
+        }
+    }
+    if (ccst >= 0) {
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (live & (1u << i)) p.cvec[i][ccst] = cst[i];
+    }
+    if ((lane & 15) == 0) {
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            redv[i * 4 * NW + wave * 4 + (lane >> 4)] = bestv[i];
+            redi[i * 4 * NW + wave * 4 + (lane >> 4)] = besti[i];
+        }
+    }
+    __syncthreads();
+    if (tid < R && (live & (1u << tid))) {  // thread i reduces member i's partials in sweep_body_gen's order
+        const double* rv = redv + tid * 4 * NW;
+        const int* ri = redi + tid * 4 * NW;
+        double bv = rv[0];
+        int bi = ri[0];
+        for (int q = 1; q < 4 * NW; ++q)
+            if (better(rv[q], ri[q], bv, bi)) {
+                bv = rv[q];
+                bi = ri[q];
+            }
+        p.pval[tid][bid] = bv;
+        p.pidx[tid][bid] = bi;
+    }
+}
+template <typename TA, int U, int R>
+__global__ __launch_bounds__(kSweepThreads) void k_sweep_multi(const MultiSweep<TA> p) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    sweep_body_multi<TA, U, 32 / U, R>(p, (int)blockIdx.x, lds);
+}
+
+// The append stages of two groups in ONE launch (the grouped scheduler's companion of k_tick's stages [0, 2G)): G workgroups per
+// k_qr2 member of group X, then G per k_qr1 member of group Y -- each signal's stage exactly as k_tick runs it.
+template <typename TA>
+struct GroupAppend {
+    TickQr2 q2[kGroupMax];
+    TickQr1<TA> q1[kGroupMax];
+    int n2, n1;
+};
+template <typename TA>
+__global__ __launch_bounds__(kSweepThreads) void k_append_group(const GroupAppend<TA> a, const int G) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int bid = (int)blockIdx.x, m = bid / G, g = bid - m * G;
+    if (m < a.n2) {
+        const TickQr2& q2 = a.q2[m];
+        qr2_body<8>(q2.Q, q2.ldq, q2.st, q2.avec, q2.r, q2.P1, q2.P1s, q2.G, q2.W1, q2.vvec, q2.P2, q2.P2s, q2.R, q2.z,
+                    q2.sel, q2.kcap, q2.jpad, q2.force_reorth, q2.jh, q2.optimistic, g, lds);
+    } else {
+        const TickQr1<TA>& q1 = a.q1[m - a.n2];
+        qr1_body<TA, 2>(q1.A, q1.ld, q1.M, q1.Q, q1.ldq, q1.st, q1.avec, q1.P1, q1.G, q1.kcap, q1.jpad, q1.mode, q1.pval,
+                        q1.pidx, q1.nblk_sweep, q1.cands, q1.ncands, q1.which, q1.sel, q1.skipmask, q1.r, q1.P1s, q1.jh, g, lds);
     }
 }
 

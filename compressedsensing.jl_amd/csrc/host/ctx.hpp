@@ -151,6 +151,8 @@ struct SpJob {
 };
 
 
+constexpr int kPairTickGrid = 192;  // sweep workgroups of each of two pipelines side by side (measured: 176 -> 6.41e3, 192 -> 6.46e3, 224 -> 6.45e3, 256 -> 6.41e3 atoms/s)
+constexpr int kSlots = 3 * kGroupMax;  // solver slots of a context: three groups of the grouped batch scheduler (host/omp.hpp)
 struct csmp_ctx {
     SpJob spjob;  // the Subspace Pursuit solve this context is carrying (csmp_sp, csmp_sp_batch, the SP functor)
     std::shared_ptr<void> omprjob;  // the OMPR object of csmp_ompr / the OMPR functor (OmprJob, host/twostage.hpp), made on first use
@@ -191,7 +193,9 @@ struct csmp_ctx {
     int tune_pair_lds_kib = 0;  // csmp_tune: dynamic LDS (KiB) of the ticks of two pipelines side by side, 0 = kPairLdsKiB (one workgroup per CU)
     int tune_pair_split = 0;    // csmp_tune: 1 = two pipelines side by side keep the fused tick (one launch), default: append stages and sweep in two launches
     int tune_fail_alloc = 0;    // csmp_tune (test hook): the n-th device allocation of a solver slot from now fails (dmalloc)
-    int tune_pipelines = 0;  // csmp_tune: 1 = csmp_omp_batch keeps ONE pipeline of three signals (default: two side by side from two signals on)
+    int tune_pipelines = 0;  // csmp_tune: 1 = csmp_omp_batch keeps ONE pipeline of three signals, 2 = two side by side, 3 = two pipelines of three GROUPS (shared sweeps); 0 = automatic
+    int tune_group_max = 0;  // csmp_tune: largest group of the grouped scheduler (0 = what the LDS holds, at most kGroupMax)
+    int sweep_group = 0;     // signals one shared sweep serves (configure_sweep; 0 where the sweep is phased or dynamic)
     int claim_pools = 8;     // counters a workgroup of the dynamic sweep finds empty in a row before it stops (its own, then the following workgroups')
     int tune_rebuild_direct = 0;  // csmp_tune: the oblivious start's Q'A pass reads its directions from L2 (k_fr_rebuild) instead of the LDS
     int tune_swap_refuse = 0;  // csmp_tune: OMPR's inverse-Gram exchanges fail their guard (tests walk the fallback to the QR path)
@@ -220,7 +224,7 @@ struct csmp_ctx {
     size_t sweep_lds_req = 0;    // the stand-alone sweep's LDS request when larger than sweep_lds (residency control)
     int tune_sweep_lds_kib = 0;  // csmp_tune
     Solver s;        // the ACTIVE solver slot (see activate_slot)
-    Solver park[3];  // parked slots (park[active] is unused): three signals are pipelined in csmp_omp_batch
+    Solver park[kSlots];  // parked slots (park[active] is unused): three signals -- or three groups of up to kGroupMax -- are pipelined in csmp_omp_batch
     int active = 0;
     bool pipeline = true;
     int tick_nblk = 0;       // absolute override of the sweep workgroup count (CSMP_TICK_NBLK), 0 = per-CU rule

@@ -179,9 +179,9 @@ static int configure_sweep(csmp_ctx* ctx) {
         ctx->sweep_KP = best_pad * rows;
     } else {
         // phases: beside the image the LDS holds the partial sums of every wave's columns (sweep_body_ph), sized for the smallest
-        // grid the sweep is launched on (the tick kernel's, or an override's)
-        int ming = std::min(ctx->sweep_grid, ctx->tick_grid);
-        if (ctx->tick_nblk > 0) ming = std::min(ming, ctx->tick_nblk);
+        // grid the sweep is launched on: the stand-alone sweep's, the tick kernel's, the pair ticks' (kPairTickGrid; an override
+        // replaces both tick grids)
+        int ming = std::min(ctx->sweep_grid, ctx->tick_nblk > 0 ? ctx->tick_nblk : std::min(ctx->tick_grid, kPairTickGrid));
         const int64_t pcap64 = (ctx->N + (int64_t)ming * 4 - 1) / ((int64_t)ming * 4);
         const int64_t spare = (int64_t)(lds_cap / sizeof(double)) - 48 - 4 * pcap64;
         const int ur = 8 * rows;
@@ -201,6 +201,16 @@ static int configure_sweep(csmp_ctx* ctx) {
     ctx->sweep_lds = ctx->sweep_ph ? sweep_ph_lds_bytes(ctx->sweep_KP, ctx->sweep_pcap)
                                    : ctx->sweep_dyn ? sweep_dyn_lds_bytes(ctx->sweep_KP) : sweep_gen_lds_bytes(ctx->sweep_KP);
     ctx->sweep_lds_req = (size_t)ctx->tune_sweep_lds_kib * 1024;
+    // shared sweeps of the grouped batch scheduler (k_sweep_multi): as many residual images as the LDS holds beside the scratch, at
+    // most kGroupMax (4096 rows f32 or f64: four; about 9000 rows f32: two).  0: no shared sweep -- the phased and the dynamic
+    // bodies serve one residual, and csmp_omp_batch keeps its pipelines of single signals.
+    ctx->sweep_group = 0;
+    if (!ctx->sweep_ph && !ctx->sweep_dyn) {
+        int g = kGroupMax;
+        while (g > 1 && sweep_multi_lds_bytes(ctx->sweep_KP, g) > lds_cap) --g;
+        if (ctx->tune_group_max > 0) g = std::min(g, ctx->tune_group_max);
+        ctx->sweep_group = g;
+    }
     // short columns: the stand-alone sweep takes several columns per unit (k_sweep_short); the tick kernel keeps the one-column body
     // (the same bits).  Units of eight loads: eight columns of one chunk (two sets of four), four of two chunks, two of three or four
     // chunks.  csmp_tune(CSMP_TUNE_SWEEP_SHORT, 1): never.
@@ -224,7 +234,7 @@ static int dict_forget(csmp_ctx* ctx) {
     }
     dict_release(ctx);  // (clones that still hold the previous dictionary keep it alive)
     HIPCHECK(sync_all(ctx));
-    for (int q = 2; q >= 0; --q) {
+    for (int q = kSlots - 1; q >= 0; --q) {
         activate_slot(ctx, q);
         solver_free(ctx->s);
     }

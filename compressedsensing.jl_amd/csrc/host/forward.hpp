@@ -369,7 +369,13 @@ static int batch_impl(csmp_ctx* ctx, int algo, const void* B, int b_dtype, int64
     // ... and where a sweep is long enough for its tail to matter: dictionaries of kPairMinBytes and more (measured: tools/probes/
     // pair_sizes.py); csmp_tune(CSMP_TUNE_PIPELINES, 2) takes two pipelines whatever the size
     const size_t dict_bytes = (size_t)ctx->Mv * (size_t)ctx->N * (ctx->dtype == CSMP_F32 ? 4 : 8);
-    if (pipe && nsig >= kPairMinSignals && ctx->tune_pipelines != 1 && (ctx->tune_pipelines == 2 || dict_bytes >= kPairMinBytes)) {
+    // GROUPED (omp only): each pipeline's three slots become three groups of up to sweep_group signals whose sweeps share one pass over
+    // A (omp_groups_pair).  csmp_tune(CSMP_TUNE_PIPELINES, 3) forces it; automatic wherever two pipelines run and a pass serves two or
+    // more signals.  Supports beyond qr_max_cols() (pipe), screened sweeps (csmp_omp_batch) and fr keep the schedules above.
+    const bool pair = pipe && nsig >= kPairMinSignals && ctx->tune_pipelines != 1 && (ctx->tune_pipelines >= 2 || dict_bytes >= kPairMinBytes);
+    const bool grouped = pair && !isfr && ctx->sweep_group >= 1 &&
+                         (ctx->tune_pipelines == 3 || (ctx->tune_pipelines == 0 && ctx->sweep_group >= 2));
+    if (pair) {
         rc = twins_ensure(ctx, 1);
         if (rc == CSMP_OK) {
             tw = ctx->twins[0];
@@ -420,7 +426,70 @@ static int batch_impl(csmp_ctx* ctx, int algo, const void* B, int b_dtype, int64
             if (r2 != CSMP_OK && c != ctx) ctx->err = c->err;
             return r2;
         };
-        if (tw && rc == CSMP_OK) {
+        auto ensure_slots = [&](csmp_ctx* c, int nslots) -> int {  // (slots 0..2 are ready: above)
+            int r2 = CSMP_OK;
+            for (int q = 3; q < nslots && r2 == CSMP_OK; ++q) {
+                activate_slot(c, q);
+                r2 = solver_ensure(c, kc, (int)k);
+            }
+            activate_slot(c, 0);
+            if (r2 != CSMP_OK && c != ctx) ctx->err = c->err;
+            return r2;
+        };
+        if (tw && grouped && rc == CSMP_OK) {
+            // the fewest shared passes: ceil(nsig / R) groups, their sizes as even as possible, dealt in rounds of six -- groups 0, 2, 4
+            // of a round to this context's pipeline, 1, 3, 5 to the twin's.  Member m of a pipeline's group g is its slot g + 3 m.
+            const int R = ctx->sweep_group;
+            const int64_t ngroups = (nsig + R - 1) / R;
+            const int64_t base = nsig / ngroups, extra = nsig % ngroups;
+            auto gsize = [&](int64_t i) { return (int)(base + (i < extra ? 1 : 0)); };
+            rc = ensure_slots(ctx, 3 * R);
+            if (rc == CSMP_OK) rc = ensure_slots(tw, 3 * R);
+            int64_t first = 0;
+            for (int64_t g0 = 0; g0 < ngroups && rc == CSMP_OK; g0 += 6) {
+                int sz[2][3] = {{0, 0, 0}, {0, 0, 0}};
+                int64_t gfirst[2][3] = {{0, 0, 0}, {0, 0, 0}};
+                csmp_ctx* cs[2] = {ctx, tw};
+                for (int64_t g = g0; g < std::min<int64_t>(g0 + 6, ngroups); ++g) {
+                    const int pl = (int)((g - g0) % 2), slot = (int)((g - g0) / 2);
+                    sz[pl][slot] = gsize(g);
+                    gfirst[pl][slot] = first;
+                    first += gsize(g);
+                }
+                for (int pl = 0; pl < 2 && rc == CSMP_OK; ++pl)
+                    for (int gg = 0; gg < 3 && rc == CSMP_OK; ++gg)
+                        for (int m = 0; m < sz[pl][gg] && rc == CSMP_OK; ++m) {
+                            csmp_ctx* c = cs[pl];
+                            activate_slot(c, gg + 3 * m);
+                            const char* col = (const char*)dB + (size_t)(gfirst[pl][gg] + m) * (size_t)ldB * es;
+                            rc = b_dtype == CSMP_F32 ? init_from_device_t<float>(c, (const float*)col) : init_from_device_t<double>(c, (const double*)col);
+                            if (rc != CSMP_OK && c != ctx) ctx->err = c->err;
+                        }
+                if (rc != CSMP_OK) break;
+                rc = ctx->dtype == CSMP_F32 ? omp_groups_pair<float>(ctx, sz[0], tw, sz[1], k, eps, opt, kPairTickGrid)
+                                            : omp_groups_pair<double>(ctx, sz[0], tw, sz[1], k, eps, opt, kPairTickGrid);
+                for (int pl = 0; pl < 2 && rc == CSMP_OK; ++pl) {
+                    for (int gg = 0; gg < 3 && rc == CSMP_OK; ++gg)
+                        for (int m = 0; m < sz[pl][gg] && rc == CSMP_OK; ++m) {
+                            csmp_ctx* c = cs[pl];
+                            const int64_t sg = gfirst[pl][gg] + m;
+                            activate_slot(c, gg + 3 * m);
+                            rc = launch_finish(c, d_idx + sg * k, d_val + sg * k, d_nnz + sg, nullptr, (int)k, sigflags + sg);
+                            if (rc != CSMP_OK && c != ctx) ctx->err = c->err;
+                        }
+                    activate_slot(cs[pl], 0);
+                }
+            }
+            sgn = nsig;
+            if (rc == CSMP_OK) {
+                HIPCHECK(hipEventRecord(tw->ev_twin, tw->stream));
+                HIPCHECK(hipStreamWaitEvent(ctx->stream, tw->ev_twin, 0));
+            } else {
+                (void)hipStreamSynchronize(tw->stream);
+                (void)hipStreamSynchronize(ctx->stream);
+            }
+        }
+        if (tw && !grouped && rc == CSMP_OK) {
             // rounds of 3 + 3 signals (this context's pipeline + the twin's), then the remainder in rounds of 1 + 1 and a last lone
             // signal: measured on the 1-GiB dictionary, atoms/s of a whole batch -- 3 + 3: 6680, 1 + 1: 6690, 2 + 2: 6486, and the
             // rounds whose pipelines hold different numbers 3 + 2: 6340, 2 + 1: 6332 (one pipeline of three: 6306, a lone signal:

@@ -98,7 +98,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     if (!ctx) return CSMP_OK;
     (void)hipSetDevice(ctx->dev);
     (void)sync_all(ctx);
-    for (int q = 2; q >= 0; --q) {
+    for (int q = kSlots - 1; q >= 0; --q) {
         activate_slot(ctx, q);
         solver_free(ctx->s);
     }

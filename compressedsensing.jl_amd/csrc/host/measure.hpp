@@ -169,6 +169,14 @@ extern "C" int csmp_sweep_config(const csmp_ctx* ctx, int* unit_loads, int* phas
     return CSMP_OK;
 }
 
+// signals one shared sweep of the grouped batch scheduler serves for the resident dictionary (0: that scheduler is not used)
+extern "C" int csmp_sweep_group(const csmp_ctx* ctx, int* group_max) {
+    if (!ctx || !group_max) return CSMP_EINVAL;
+    if (!ctx->dA) return CSMP_ESTATE;
+    *group_max = ctx->sweep_group;
+    return CSMP_OK;
+}
+
 extern "C" int csmp_tune(csmp_ctx* ctx, int key, int64_t value) {
     if (!ctx) return CSMP_EINVAL;
     if (value < 0 || value > (1 << 20)) return fail(ctx, CSMP_EINVAL, "csmp_tune: value out of range");
@@ -200,8 +208,12 @@ extern "C" int csmp_tune(csmp_ctx* ctx, int key, int64_t value) {
         case CSMP_TUNE_SCREEN_STATIC: ctx->tune_screen_static = value == 1 ? 1 : 0; return CSMP_OK;
         case CSMP_TUNE_PAIR_SPLIT: ctx->tune_pair_split = value == 1 ? 1 : 0; return CSMP_OK;
         case CSMP_TUNE_FAIL_ALLOC: ctx->tune_fail_alloc = (int)value; return CSMP_OK;
+        case CSMP_TUNE_GROUP_MAX:
+            if (value > kGroupMax) return fail(ctx, CSMP_EINVAL, "csmp_tune: group_max must be 0 (what the LDS holds) or 1 .. 4");
+            ctx->tune_group_max = (int)value;
+            break;
         case CSMP_TUNE_PIPELINES:
-            if (value > 2) return fail(ctx, CSMP_EINVAL, "csmp_tune: pipelines must be 0 (automatic), 1 or 2");
+            if (value > 3) return fail(ctx, CSMP_EINVAL, "csmp_tune: pipelines must be 0 (automatic), 1, 2 or 3");
             ctx->tune_pipelines = (int)value;
             return CSMP_OK;
         case CSMP_TUNE_TICK_ORDER: ctx->tick_sweep_first = value != 0; return CSMP_OK;

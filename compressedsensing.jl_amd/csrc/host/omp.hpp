@@ -148,7 +148,6 @@ static int omp_ticks(csmp_ctx* ctx, const bool present[3], int64_t k, double eps
     return CSMP_OK;
 }
 constexpr int kPairLdsKiB = 81;     // dynamic LDS of a tick of two pipelines side by side: more than half a CU's 160 KiB = one workgroup per CU
-constexpr int kPairTickGrid = 192;  // sweep workgroups of each of two pipelines side by side (measured: 176 -> 6.41e3, 192 -> 6.46e3, 224 -> 6.45e3, 256 -> 6.41e3 atoms/s)
 // TWO pipelines side by side: a second triple of signals on a twin context (its own stream), the launches of the two enqueued
 // alternately.  The sweeps of the two then share the HBM, out of step with one another: the last workgroups of one tick, its
 // launch boundary and the staging of its residual image fall under the other pipeline's stream instead of leaving the memory
@@ -175,6 +174,121 @@ static int omp_ticks_pair(csmp_ctx* a, const bool pa[3], csmp_ctx* b, const bool
     for (int64_t n = 0; n < 3 * k + 2; ++n) {
         CHECK(tick_pipe_launch<TA>(ta, n, k, eps, optimistic));
         const int rc = tick_pipe_launch<TA>(tb, n, k, eps, optimistic);
+        if (rc != CSMP_OK) {
+            a->err = b->err;
+            return rc;
+        }
+    }
+    return CSMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------ grouped scheduler (shared sweeps)
+// omp_ticks_pair's rotation with three GROUPS of up to ctx->sweep_group signals per pipeline in place of three signals: at tick n
+// the members of group n % 3 sweep in ONE launch that reads A once for all of them (k_sweep_multi), and the k_qr1 stages of group
+// (n + 2) % 3 and the k_qr2 stages of group (n + 1) % 3 run in ONE append launch (k_append_group), small enough to share the CUs
+// with the other pipeline's sweep.  Every signal's own chain -- sweep, qr1, qr2 in three consecutive ticks -- is the one omp_ticks
+// runs, so every signal gets the same bits.  Member m of group g is solver slot g + 3 m (slot 0 is the active one).
+struct GroupPipe {
+    csmp_ctx* ctx = nullptr;
+    int size[3] = {0, 0, 0};  // members of each group (0: the group is absent)
+    int nblk = 0;
+    size_t lds_app = 0;  // the append launch's request
+    size_t excl = 0;     // the sweep launch's smallest request: one workgroup per CU (kPairLdsKiB)
+};
+static Solver* slot_ptr(csmp_ctx* ctx, int q) { return q == 0 ? &ctx->s : &ctx->park[q]; }
+template <typename TA, int U, int R>
+static hipError_t multi_launch_t(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t lds) {
+    auto kern = k_sweep_multi<TA, U, R>;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(kSweepThreads), lds, ctx->stream, p);
+    return hipGetLastError();
+}
+template <typename TA, int U>
+static hipError_t multi_launch_u(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t lds) {
+    switch (p.n) {
+        case 1: return multi_launch_t<TA, U, 1>(ctx, p, lds);
+        case 2: return multi_launch_t<TA, U, 2>(ctx, p, lds);
+        case 3: return multi_launch_t<TA, U, 3>(ctx, p, lds);
+        default: return multi_launch_t<TA, U, 4>(ctx, p, lds);
+    }
+}
+template <typename TA>
+static hipError_t multi_launch(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t lds) {
+    switch (ctx->sweep_U) {
+        case 16: return multi_launch_u<TA, 16>(ctx, p, lds);
+        case 8: return multi_launch_u<TA, 8>(ctx, p, lds);
+        default: return multi_launch_u<TA, 4>(ctx, p, lds);
+    }
+}
+static void group_pipe_begin(GroupPipe& gp, csmp_ctx* ctx, const int size[3], int64_t k, int grid) {
+    gp.ctx = ctx;
+    for (int g = 0; g < 3; ++g) gp.size[g] = size[g];
+    activate_slot(ctx, 0);
+    const int64_t groups = (ctx->N + (kSweepThreads / kWave) - 1) / (kSweepThreads / kWave);
+    gp.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ctx->tick_nblk > 0 ? ctx->tick_nblk : grid, groups),
+                                                         ctx->prop.multiProcessorCount * 8 + 8));  // (pval / pidx: solver_alloc)
+    gp.lds_app = qr_lds_bytes((int)std::min<int64_t>(k, ctx->s.kcap));
+    gp.excl = (size_t)(ctx->tune_pair_lds_kib > 0 ? ctx->tune_pair_lds_kib : kPairLdsKiB) * 1024;
+}
+template <typename TA>
+static int group_pipe_launch(GroupPipe& gp, int64_t n, int64_t k, double eps, bool optimistic) {
+    csmp_ctx* ctx = gp.ctx;
+    const int skip = STOP_EPS | STOP_STAG | STOP_FULL | STOP_REORTH;
+    const int zs = (int)(n % 3), ys = (int)((n + 2) % 3), xs = (int)((n + 1) % 3);  // sweep, qr1, qr2 groups
+    const int64_t tz = (n - zs) / 3, ty = (n - 1 - ys) / 3, tx = (n - 2 - xs) / 3;
+    const bool az = gp.size[zs] > 0 && n >= zs && tz < k;
+    const bool ay = gp.size[ys] > 0 && n >= 1 + ys && ty < k && (n - 1 - ys) % 3 == 0;
+    const bool ax = gp.size[xs] > 0 && n >= 2 + xs && tx < k && (n - 2 - xs) % 3 == 0;
+    if (ay || ax) {
+        GroupAppend<TA> a;
+        a.n2 = ax ? gp.size[xs] : 0;
+        a.n1 = ay ? gp.size[ys] : 0;
+        for (int m = 0; m < a.n2; ++m) {
+            const Solver& s = *slot_ptr(ctx, xs + 3 * m);
+            a.q2[m] = tick_qr2_params(ctx, s, s.jh_last, optimistic ? 1 : 0, 1);
+        }
+        for (int m = 0; m < a.n1; ++m) {
+            Solver& s = *slot_ptr(ctx, ys + 3 * m);
+            const int jh1 = std::min(s.jh, s.kcap);
+            s.jh_last = jh1;
+            if (s.jh < s.kcap) s.jh += 1;
+            a.q1[m] = tick_qr1_params<TA>(ctx, s, skip, gp.nblk, jh1, 1);
+        }
+        const int G = ctx->s.G;
+        auto kern = k_append_group<TA>;
+        if (gp.lds_app > 64 * 1024) HIPCHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gp.lds_app));
+        hipLaunchKernelGGL(kern, dim3((a.n1 + a.n2) * G), dim3(kSweepThreads), gp.lds_app, ctx->stream, a, G);
+        HIPCHECK(hipGetLastError());
+    }
+    if (az) {
+        MultiSweep<TA> p;
+        p.A = (const TA*)ctx->dA; p.ld = ctx->ld; p.Mv = ctx->Mv; p.N = ctx->N;
+        p.eps = eps; p.check_eps = tz > 0 ? 1 : 0; p.skipmask = skip; p.nblk = gp.nblk; p.KP = ctx->sweep_KP;
+        p.n = gp.size[zs];
+        for (int m = 0; m < kGroupMax; ++m) {
+            const Solver& s = *slot_ptr(ctx, zs + 3 * std::min(m, p.n - 1));  // (entries past n are never read)
+            p.r[m] = s.r; p.cvec[m] = s.cvec; p.pval[m] = s.pval; p.pidx[m] = s.pidx; p.st[m] = s.st;
+        }
+        // ONE sampled launch per shared pass: it reads A once, whatever the group size
+        const bool timed = prof_pick(ctx);
+        if (timed) CHECK(prof_mark(ctx));
+        HIPCHECK(multi_launch<TA>(ctx, p, std::max(sweep_multi_lds_bytes(p.KP, p.n), gp.excl)));
+        if (timed) CHECK(prof_mark(ctx));
+    }
+    return CSMP_OK;
+}
+// Two grouped pipelines side by side (b may carry no group), their launches enqueued alternately as in omp_ticks_pair.
+template <typename TA>
+static int omp_groups_pair(csmp_ctx* a, const int sa[3], csmp_ctx* b, const int sb[3], int64_t k, double eps, bool optimistic, int grid) {
+    GroupPipe ga, gb;
+    group_pipe_begin(ga, a, sa, k, grid);
+    group_pipe_begin(gb, b, sb, k, grid);
+    for (int64_t n = 0; n < 3 * k + 2; ++n) {
+        CHECK(group_pipe_launch<TA>(ga, n, k, eps, optimistic));
+        const int rc = group_pipe_launch<TA>(gb, n, k, eps, optimistic);
         if (rc != CSMP_OK) {
             a->err = b->err;
             return rc;

@@ -35,12 +35,16 @@ int csmp_bench_sweep(csmp_ctx *ctx, int variant, int reps, double *avg_ms);
  * where the stand-alone sweep takes short columns several at a time (k_sweep_short), else 1.  Any pointer may be NULL. */
 int csmp_sweep_config(const csmp_ctx *ctx, int *unit_loads, int *phases, int *workgroups, int *tick_workgroups, int64_t *lds_bytes, int *dynamic,
                       int *columns_per_unit);
+/* signals one shared sweep of csmp_omp_batch's grouped scheduler serves for the resident dictionary (k_sweep_multi: one LDS image of
+ * the residual per signal, at most 4); 0 = no shared sweep for this dictionary (a phased or dynamic sweep): that scheduler is not used */
+int csmp_sweep_group(const csmp_ctx *ctx, int *group_max);
 /* measurement overrides of that choice, applied to the resident dictionary at once and to later ones: 0 = automatic */
 #define CSMP_TUNE_SWEEP_GRID 2   /* workgroups of the product sweep */
 #define CSMP_TUNE_SWEEP_UNIT 3   /* loads per unit (16, 8 or 4) */
 #define CSMP_TUNE_TICK_GRID 4    /* sweep workgroups inside the tick kernel of csmp_omp_batch */
 #define CSMP_TUNE_SWEEP_DYN 9     /* 1: the product sweep hands its columns out at run time (k_sweep_dyn; one LDS image, grids up to 512 workgroups); n = 2..64: only the last 1 / n of a workgroup's columns, after a static head; default 0: the static split */
-#define CSMP_TUNE_PIPELINES 12    /* 1: csmp_omp_batch keeps one pipeline of three signals; 2: two pipelines side by side whatever the sizes; default 0: two from two signals and a 4-MiB dictionary on (rounds of 3 + 3 signals, the remainder 1 + 1) */
+#define CSMP_TUNE_PIPELINES 12    /* 1: csmp_omp_batch keeps one pipeline of three signals; 2: two pipelines side by side whatever the sizes (rounds of 3 + 3 signals, the remainder 1 + 1); 3: two pipelines of three GROUPS of signals, each group's sweeps one shared pass over A (k_sweep_multi); default 0: 3 where a shared pass serves two or more signals, else 2, from two signals and a 4-MiB dictionary on; 3 falls back to 2 where no shared sweep exists */
+#define CSMP_TUNE_GROUP_MAX 20    /* largest group of the grouped scheduler (CSMP_TUNE_PIPELINES 3); 0 = as many residual images as the LDS holds, at most 4 */
 #define CSMP_TUNE_TICK_ORDER 10   /* 1: the tick kernel's sweep workgroups are dispatched ahead of its append stages' */
 #define CSMP_TUNE_CLAIM_POOLS 11  /* the dynamic sweep: column pools a workgroup may claim from (its own first) */
 #define CSMP_TUNE_PAIR_LDS_KIB 13 /* dynamic LDS (KiB) requested by the ticks of two pipelines side by side: above 80 = one workgroup per CU (default 81), 1 = what the kernels need */
