@@ -1,0 +1,96 @@
+// host/batch_plan.hpp -- the schedules of csmp_omp_batch / csmp_fr_batch as data: the stage rotation of a tick pipeline and the
+// rounds a batch runs in (host/forward.hpp: batch_impl).  Plain C++, no HIP: included by csmp.hip (the library) and, alone, by
+// tools/sanitize/hostonly_driver.cpp, which checks every plan a batch of up to 64 signals can get.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+// A pipeline holds three groups of signals (a group of the grouped schedule has up to sweep_group members, every other schedule's
+// one or none).  At tick n group n % 3 sweeps, group (n + 2) % 3 runs its k_qr1 stage and group (n + 1) % 3 its k_qr2 stage: every
+// signal's chain -- sweep, qr1, qr2 in three consecutive ticks -- takes one step in three ticks, k steps in 3k + 2 ticks.
+struct TickStages {
+    int z, y, x;       // the sweep, qr1 and qr2 groups
+    bool az, ay, ax;   // ... whether each is live (a group of size 0 never is)
+    int64_t tz;        // the sweep's step
+};
+static TickStages tick_stages(int64_t n, int64_t k, const int size[3]) {
+    TickStages t;
+    t.z = (int)(n % 3);
+    t.y = (int)((n + 2) % 3);
+    t.x = (int)((n + 1) % 3);
+    t.tz = (n - t.z) / 3;
+    t.az = size[t.z] > 0 && t.tz < k;
+    t.ay = size[t.y] > 0 && n >= 1 + t.y && (n - 1 - t.y) / 3 < k;
+    t.ax = size[t.x] > 0 && n >= 2 + t.x && (n - 2 - t.x) / 3 < k;
+    return t;
+}
+
+enum class BatchSchedule {
+    Signals,  // no pipeline: one signal after the other
+    One,      // one pipeline of three signals
+    Pairs,    // two pipelines side by side, the second on a twin context
+    Grouped,  // two pipelines of three groups whose members share one sweep
+};
+enum class RoundForm { One, Pair, Grouped };  // how a round's ticks are launched
+struct PlanGroup {
+    int64_t first = 0;  // the group's first signal; its members are the signals first .. first + size - 1
+    int size = 0;
+};
+struct PlanRound {
+    RoundForm form = RoundForm::One;
+    PlanGroup g[2][3];  // [pipeline: 0 = A, the caller's context; 1 = B, the twin][group]; member m of group g is solver slot g + 3 m
+};
+
+// The rounds of a batch of nsig signals (R: the members a shared sweep serves, ctx->sweep_group).  Pairs: rounds of 3 + 3 while six or
+// more signals remain, then 1 + 1, then a lone signal in the one-pipeline form.  Grouped: the fewest shared passes -- ceil(nsig / R)
+// groups of consecutive signals, their sizes as even as possible -- dealt six to a round, even offsets to A and odd ones to B; a last
+// round may leave B with no group and keeps the pair form.
+static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int R) {
+    std::vector<PlanRound> rounds;
+    auto round = [&](RoundForm form) -> PlanRound& {
+        rounds.emplace_back();
+        rounds.back().form = form;
+        return rounds.back();
+    };
+    int64_t at = 0;
+    switch (sched) {
+        case BatchSchedule::Signals: break;
+        case BatchSchedule::One:
+            for (; at < nsig; at += 3) {
+                PlanRound& r = round(RoundForm::One);
+                for (int g = 0; g < 3 && at + g < nsig; ++g) r.g[0][g] = {at + g, 1};
+            }
+            break;
+        case BatchSchedule::Pairs:
+            // measured on the 1-GiB dictionary, atoms/s of a whole batch -- 3 + 3: 6680, 1 + 1: 6690, 2 + 2: 6486, and the rounds whose
+            // pipelines hold different numbers 3 + 2: 6340, 2 + 1: 6332 (one pipeline of three: 6306, a lone signal: 5830;
+            // tools/probes/few_signals.sh).  Two streams with a sweep ready each keep the HBM busy; what costs is a round in which one
+            // stream's ticks have sweeps the other's have not.
+            for (; nsig - at >= 6; at += 6) {
+                PlanRound& r = round(RoundForm::Pair);
+                for (int g = 0; g < 3; ++g) {
+                    r.g[0][g] = {at + g, 1};
+                    r.g[1][g] = {at + 3 + g, 1};
+                }
+            }
+            for (; nsig - at >= 2; at += 2) {
+                PlanRound& r = round(RoundForm::Pair);
+                r.g[0][0] = {at, 1};
+                r.g[1][0] = {at + 1, 1};
+            }
+            if (at < nsig) round(RoundForm::One).g[0][0] = {at, 1};
+            break;
+        case BatchSchedule::Grouped: {
+            if (nsig < 1 || R < 1) break;
+            const int64_t ngroups = (nsig + R - 1) / R, base = nsig / ngroups, extra = nsig % ngroups;
+            for (int64_t i = 0; i < ngroups; ++i) {
+                if (i % 6 == 0) round(RoundForm::Grouped);
+                const int size = (int)(base + (i < extra ? 1 : 0));
+                rounds.back().g[i % 2][(i % 6) / 2] = {at, size};
+                at += size;
+            }
+            break;
+        }
+    }
+    return rounds;
+}

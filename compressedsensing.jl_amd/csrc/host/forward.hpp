@@ -166,8 +166,8 @@ static int fr_step(csmp_ctx* ctx, bool first, double max_eps, double min_d2, boo
     return launch_append(ctx, 3, 0, skip, optimistic, min_d2, ctx->s.fr_grid);
 }
 
-// Forward regression for up to three signals advanced together (the omp_ticks schedule with the OLS sweep):
-// at tick n slot n%3 sweeps, slot (n-1)%3 runs its k_qr1 stage (mode 3), slot (n-2)%3 its k_qr2 stage.
+// One tick of a pipeline of three forward-regression signals (tick_pipe_launch, host/omp.hpp, with the OLS sweep: k_tick_fr,
+// the qr1 stage in mode 3)
 template <typename TA, int U, int NQ>
 static hipError_t tick_fr_launch_t(csmp_ctx* ctx, const TickFr<TA>& sw, const TickQr1<TA>& q1, const TickQr2& q2, int G, size_t lds,
                                    double min_d2) {
@@ -179,84 +179,29 @@ static hipError_t tick_fr_launch_t(csmp_ctx* ctx, const TickFr<TA>& sw, const Ti
     hipLaunchKernelGGL(kern, dim3(2 * G + sw.nblk), dim3(kSweepThreads), lds, ctx->stream, sw, q1, q2, G, min_d2);
     return hipGetLastError();
 }
-// One pipeline's schedule (the TickPipe of host/omp.hpp with the OLS sweep)
-struct FrPipe {
-    csmp_ctx* ctx = nullptr;
-    bool present[3] = {false, false, false};
-    int nblk = 0, U = 8;
-    size_t lds = 0;
-};
-static void fr_pipe_begin(FrPipe& fp, csmp_ctx* ctx, const bool present[3], int64_t k) {
-    fp.ctx = ctx;
-    for (int q = 0; q < 3; ++q) fp.present[q] = present[q];
-    activate_slot(ctx, 0);
-    int grid; bool full; size_t flds;
-    fr_config(ctx, 1, fp.U, full, flds, grid);
-    fp.nblk = grid;
-    fp.lds = std::max(flds, qr_lds_bytes((int)std::min<int64_t>(k, ctx->s.kcap)));
-}
 template <typename TA>
-static int fr_pipe_launch(FrPipe& fp, int64_t n, int64_t k, double max_eps, double min_d2, bool optimistic) {
+static int fr_pipe_launch(Pipe& fp, int64_t n) {
     csmp_ctx* ctx = fp.ctx;
     const int skip = STOP_EPS | STOP_STAG | STOP_FULL | STOP_REORTH;
-    Solver* sl[3] = {&ctx->s, &ctx->park[1], &ctx->park[2]};  // (slot 0 is the active one: fr_pipe_begin)
-    const int G = sl[0]->G;
-    const int zs = (int)(n % 3), ys = (int)((n + 2) % 3), xs = (int)((n + 1) % 3);
-    const int64_t tz = (n - zs) / 3, ty = (n - 1 - ys) / 3, tx = (n - 2 - xs) / 3;
-    const bool az = fp.present[zs] && n >= zs && tz < k;
-    const bool ay = fp.present[ys] && n >= 1 + ys && ty < k && (n - 1 - ys) % 3 == 0;
-    const bool ax = fp.present[xs] && n >= 2 + xs && tx < k && (n - 2 - xs) % 3 == 0;
-    if (!az && !ay && !ax) return CSMP_OK;
-    int jh1 = 0;
-    if (ay) {
-        jh1 = std::min(sl[ys]->jh, sl[ys]->kcap);
-        sl[ys]->jh_last = jh1;
-        if (sl[ys]->jh < sl[ys]->kcap) sl[ys]->jh += 1;
-    }
-    const Solver& z = *sl[zs];
+    const TickStages t = tick_stages(n, fp.k, fp.size);
+    if (!t.az && !t.ay && !t.ax) return CSMP_OK;
+    Solver &z = *slot_ptr(ctx, t.z), &y = *slot_ptr(ctx, t.y), &x = *slot_ptr(ctx, t.x);
+    const int G = ctx->s.G;
+    const int jh1 = t.ay ? qr1_advance(y) : 0;
     TickFr<TA> sw;
     sw.A = (const TA*)ctx->dA; sw.ld = ctx->ld; sw.Mv = ctx->Mv; sw.N = ctx->N;
     sw.r = z.r; sw.Q = z.Q; sw.ldq = z.ldq; sw.rho2 = z.rho2; sw.dvec = z.dvec; sw.pval = z.pval; sw.pidx = z.pidx;
-    sw.sel = z.sel; sw.st = z.st; sw.max_eps = max_eps; sw.skipmask = skip; sw.nblk = fp.nblk; sw.active = az ? 1 : 0;
-    auto q1 = tick_qr1_params<TA>(ctx, *sl[ys], skip, fp.nblk, jh1, ay ? 1 : 0);
+    sw.sel = z.sel; sw.st = z.st; sw.max_eps = fp.eps; sw.skipmask = skip; sw.nblk = fp.nblk; sw.active = t.az ? 1 : 0;
+    auto q1 = tick_qr1_params<TA>(ctx, y, skip, fp.nblk, jh1, t.ay ? 1 : 0);
     q1.mode = 3;
-    auto q2 = tick_qr2_params(ctx, *sl[xs], sl[xs]->jh_last, optimistic ? 1 : 0, ax ? 1 : 0);
-    auto launch = [&](const TickFr<TA>& s_, const TickQr1<TA>& a_, const TickQr2& b_, int g_, size_t lds_) -> hipError_t {
-        if (fp.U == 16)
-            return tz == 0 ? tick_fr_launch_t<TA, 16, -1>(ctx, s_, a_, b_, g_, lds_, min_d2) : tick_fr_launch_t<TA, 16, 1>(ctx, s_, a_, b_, g_, lds_, min_d2);
-        return tz == 0 ? tick_fr_launch_t<TA, 8, -1>(ctx, s_, a_, b_, g_, lds_, min_d2) : tick_fr_launch_t<TA, 8, 1>(ctx, s_, a_, b_, g_, lds_, min_d2);
-    };
-    const bool timed = az && ay && ax && prof_pick(ctx);
+    const auto q2 = tick_qr2_params(ctx, x, x.jh_last, 1, t.ax ? 1 : 0);
+    const double d2 = fp.min_d2;
+    const bool timed = t.az && t.ay && t.ax && prof_pick(ctx);
     if (timed) CHECK(prof_mark(ctx));
-    HIPCHECK(launch(sw, q1, q2, G, fp.lds));
+    const hipError_t e = fp.U == 16 ? (t.tz == 0 ? tick_fr_launch_t<TA, 16, -1>(ctx, sw, q1, q2, G, fp.lds, d2) : tick_fr_launch_t<TA, 16, 1>(ctx, sw, q1, q2, G, fp.lds, d2))
+                                    : (t.tz == 0 ? tick_fr_launch_t<TA, 8, -1>(ctx, sw, q1, q2, G, fp.lds, d2) : tick_fr_launch_t<TA, 8, 1>(ctx, sw, q1, q2, G, fp.lds, d2));
+    HIPCHECK(e);
     if (timed) CHECK(prof_mark(ctx));
-    return CSMP_OK;
-}
-template <typename TA>
-static int fr_ticks(csmp_ctx* ctx, const bool present[3], int64_t k, double max_eps, double min_d2, bool optimistic) {
-    FrPipe fp;
-    fr_pipe_begin(fp, ctx, present, k);
-    for (int64_t n = 0; n < 3 * k + 2; ++n) CHECK(fr_pipe_launch<TA>(fp, n, k, max_eps, min_d2, optimistic));
-    return CSMP_OK;
-}
-// Two such pipelines side by side (the omp_ticks_pair of host/omp.hpp with the OLS sweep): the ticks of both ask for lds_req bytes of
-// LDS -- above half a CU's, one workgroup per CU -- so that the two streams' workgroups queue for the CUs
-template <typename TA>
-static int fr_ticks_pair(csmp_ctx* ca, const bool pa[3], csmp_ctx* cb, const bool pb[3], int64_t k, double max_eps, double min_d2,
-                         bool optimistic, size_t lds_req) {
-    FrPipe fa, fb;
-    fr_pipe_begin(fa, ca, pa, k);
-    fr_pipe_begin(fb, cb, pb, k);
-    fa.lds = std::max(fa.lds, lds_req);
-    fb.lds = std::max(fb.lds, lds_req);
-    for (int64_t n = 0; n < 3 * k + 2; ++n) {
-        CHECK(fr_pipe_launch<TA>(fa, n, k, max_eps, min_d2, optimistic));
-        const int rb = fr_pipe_launch<TA>(fb, n, k, max_eps, min_d2, optimistic);
-        if (rb != CSMP_OK) {
-            ca->err = cb->err;
-            return rb;
-        }
-    }
     return CSMP_OK;
 }
 // fr(A, b, max_ε, min_δ, k) = ols = oomp = ormp, x starting empty: src/forward.jl:44-54
@@ -293,6 +238,90 @@ extern "C" int csmp_fr(csmp_ctx* ctx, const void* b, int b_dtype, int64_t k, dou
     }
     CHECK(download_result(ctx, ctx->s.outcap, idx, val, nnz, order));
     return CSMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------ omp / fr batch
+// Optimistic two-kernel append chains for every signal, no host synchronisation.  Signals are taken three at a time through the
+// tick kernel (k_tick): one launch per atom carries the sweep of one signal and the two short append stages of the other two, so
+// the latency-bound chain is hidden underneath the HBM-bound sweep.  Bit-identical to the one-at-a-time path.
+static BatchSchedule batch_schedule(const csmp_ctx* ctx, bool isfr, int64_t nsig, int kc) {
+    // (the tick kernel carries the LDS form of the append stages: supports beyond qr_max_cols() go one signal at a time through
+    // launch_append, whose spill kernels have no such bound)
+    if (!ctx->pipeline || nsig < 2 || kc > qr_max_cols()) return BatchSchedule::Signals;
+    if (isfr) {  // the tick kernel exists for the exact-tiling FR sweeps only
+        int U, g; bool full; size_t l;
+        fr_config(ctx, 1, U, full, l, g);
+        if (!full || fr_tall(ctx, 1)) return BatchSchedule::Signals;
+    }
+    // TWO pipelines: the second half of the triples runs on a twin context and stream beside the first.  The sweeps of the two then
+    // share the HBM, out of step with one another: the last workgroups of one tick, its launch boundary and the staging of its
+    // residual image fall under the other pipeline's stream instead of leaving the memory system idle (DESIGN.md section 0, round 6:
+    // 6.03e3 -> 6.46e3 atoms/s with 192 sweep workgroups each).
+    // From two signals on and dictionaries of 4 MiB on; csmp_tune(CSMP_TUNE_PIPELINES, 1) keeps one, 2 takes two whatever the size.
+    // (forward regression too: its ticks under the same LDS request -- one workgroup per CU -- 6.28e3 -> 6.57e3 atoms/s at the benchmark
+    // shape; without the request 6.47e3.  With the sweep body as round 5 left it the same pairing had measured 5.99e3 against 5.96e3.)
+    // ... and where a sweep is long enough for its tail to matter: dictionaries of kPairMinBytes and more (measured: tools/probes/
+    // pair_sizes.py)
+    constexpr int64_t kPairMinSignals = 2;
+    constexpr size_t kPairMinBytes = (size_t)4 << 20;  // two pipelines: 1 MiB -10 %, 8 MiB +35 %, 32 MiB +40 %, 64 MiB ... 1 GiB +5 ... +16 %
+    const size_t dict_bytes = (size_t)ctx->Mv * (size_t)ctx->N * (ctx->dtype == CSMP_F32 ? 4 : 8);
+    if (nsig < kPairMinSignals || ctx->tune_pipelines == 1 || (ctx->tune_pipelines < 2 && dict_bytes < kPairMinBytes)) return BatchSchedule::One;
+    // GROUPED (omp only): each pipeline's three slots become three groups of up to sweep_group signals whose sweeps share one pass over
+    // A (group_pipe_launch).  csmp_tune(CSMP_TUNE_PIPELINES, 3) forces it; automatic wherever two pipelines run and a pass serves two or
+    // more signals.  Supports beyond qr_max_cols(), screened sweeps (csmp_omp_batch) and fr keep the schedules above.
+    if (!isfr && ctx->sweep_group >= 1 && (ctx->tune_pipelines == 3 || (ctx->tune_pipelines == 0 && ctx->sweep_group >= 2)))
+        return BatchSchedule::Grouped;
+    return BatchSchedule::Pairs;
+}
+
+constexpr int kPairLdsKiB = 81;  // dynamic LDS of a tick of two pipelines side by side: more than half a CU's 160 KiB = one workgroup per CU
+// A pipeline of a round on context c: its groups, its sweep grid and its LDS requests
+static void pipe_begin(Pipe& p, csmp_ctx* c, const PlanGroup g[3], RoundForm form, bool isfr, int64_t k, double eps, double min_d2) {
+    p.ctx = c;
+    for (int q = 0; q < 3; ++q) p.size[q] = g[q].size;
+    p.k = k;
+    p.eps = eps;
+    p.min_d2 = min_d2;
+    activate_slot(c, 0);
+    const size_t qr_lds = qr_lds_bytes((int)std::min<int64_t>(k, c->s.kcap));  // (jh never exceeds k here)
+    // Two pipelines: ONE workgroup per CU (an LDS request above half of the 160 KiB): the workgroups of the two pipelines' launches
+    // then QUEUE for the CUs instead of all being resident at once, and the dispatcher hands a CU that a workgroup of one tick has left
+    // to the next workgroup in line -- of the other pipeline's tick, whose sweep does not depend on this one.  The chip is never waiting
+    // for the slowest workgroups of a launch (they finish 139 ... 160 us into a 157-us sweep), for a launch boundary or for a residual
+    // image.
+    const size_t excl = form == RoundForm::One ? 0 : (size_t)(c->tune_pair_lds_kib > 0 ? c->tune_pair_lds_kib : kPairLdsKiB) * 1024;
+    if (isfr) {
+        bool full;
+        size_t flds;
+        fr_config(c, 1, p.U, full, flds, p.nblk);
+        p.lds = std::max({flds, qr_lds, excl});
+        return;
+    }
+    // Measured at 4096 x 65536 f32: 8-chunk load blocks on ONE workgroup per CU (the append stages of the other two signals share
+    // those CUs) 160.4 us per tick; 16-chunk blocks on 176 workgroups (11/12 of the stand-alone sweep's optimum of 192) 162.6 us.
+    p.nblk = pipe_nblk(c, form == RoundForm::One ? c->tick_grid : kPairTickGrid);  // (tick_grid: configure_sweep)
+    if (form == RoundForm::Grouped) {
+        p.lds = qr_lds;
+        p.lds_sweep = excl;
+    } else if (form == RoundForm::One || c->tune_pair_split == 1) {  // (pair_split 1, a measurement: the fused tick under the large request)
+        p.lds = std::max({c->sweep_lds, qr_lds, excl});
+    } else {  // a tick of two pipelines is two launches: the append stages under what THEY need, the sweep one workgroup per CU
+        p.lds = qr_lds;
+        p.lds_sweep = std::max(c->sweep_lds, excl);
+    }
+}
+// One round of the plan: pipeline A on ctx, in the pair and grouped forms pipeline B on the twin beside it
+template <typename TA>
+static int run_round(const PlanRound& r, csmp_ctx* ctx, csmp_ctx* tw, bool isfr, int64_t k, double eps, double min_d2) {
+    Pipe a, b;
+    pipe_begin(a, ctx, r.g[0], r.form, isfr, k, eps, min_d2);
+    Pipe* pb = nullptr;
+    if (r.form != RoundForm::One) {
+        pipe_begin(b, tw, r.g[1], r.form, isfr, k, eps, min_d2);
+        pb = &b;
+    }
+    if (r.form == RoundForm::Grouped) return pipe_ticks<group_pipe_launch<TA>>(a, pb);
+    return isfr ? pipe_ticks<fr_pipe_launch<TA>>(a, pb) : pipe_ticks<tick_pipe_launch<TA>>(a, pb);
 }
 
 // omp (algo = CSMP_ALGO_OMP: p1 = eps) or fr (CSMP_ALGO_FR: p1 = max_eps, p2 = min_delta^2) for every column of B
@@ -336,216 +365,89 @@ static int batch_impl(csmp_ctx* ctx, int algo, const void* B, int b_dtype, int64
         ctx->s.sigcap = (int)nsig;
     }
     int* const sigflags = ctx->s.sigflags;  // (a pointer VALUE: ctx->s itself is swapped by activate_slot)
-    auto solve_one = [&](int64_t sgn, bool optimistic) -> int {
+    auto init = [&](csmp_ctx* c, int64_t sgn) -> int {  // signal sgn into c's active slot
         const char* col = (const char*)dB + (size_t)sgn * (size_t)ldB * es;
-        int r2 = b_dtype == CSMP_F32 ? init_from_device_t<float>(ctx, (const float*)col)
-                                     : init_from_device_t<double>(ctx, (const double*)col);
+        return b_dtype == CSMP_F32 ? init_from_device_t<float>(c, (const float*)col) : init_from_device_t<double>(c, (const double*)col);
+    };
+    auto finish = [&](csmp_ctx* c, int64_t sgn) -> int {
+        return launch_finish(c, d_idx + sgn * k, d_val + sgn * k, d_nnz + sgn, nullptr, (int)k, sigflags + sgn);
+    };
+    auto solve_one = [&](int64_t sgn, bool optimistic) -> int {
+        int r2 = init(ctx, sgn);
         for (int64_t t = 0; t < k && r2 == CSMP_OK; ++t)
             r2 = isfr ? fr_step(ctx, t == 0, eps, p2, optimistic) : omp_step(ctx, eps, t > 0, optimistic);
-        if (r2 == CSMP_OK) r2 = launch_finish(ctx, d_idx + sgn * k, d_val + sgn * k, d_nnz + sgn, nullptr, (int)k, sigflags + sgn);
+        if (r2 == CSMP_OK) r2 = finish(ctx, sgn);
         return r2;
     };
-    // optimistic two-kernel append chain for every signal, no host synchronisation.  Signals are
-    // taken three at a time through the tick kernel (k_tick): one launch per atom carries the sweep
-    // of one signal and the two short append stages of the other two, so the latency-bound chain
-    // is hidden underneath the HBM-bound sweep.  Bit-identical to the one-at-a-time path.
-    const bool opt = true;
-    // (the tick kernel carries the LDS form of the append stages: supports beyond qr_max_cols() go one signal at a time through
-    // launch_append, whose spill kernels have no such bound)
-    bool pipe = ctx->pipeline && nsig >= 2 && kc <= qr_max_cols();
-    if (isfr) {  // the tick kernel exists for the exact-tiling FR sweeps only
-        int U, g; bool full; size_t l;
-        fr_config(ctx, 1, U, full, l, g);
-        pipe = pipe && full && !fr_tall(ctx, 1);
-    }
-    int64_t sgn = 0;
-    // TWO pipelines: the second half of the triples runs on a twin context and stream beside the first (omp_ticks_pair, fr_ticks_pair).
-    // From two signals on and dictionaries of 4 MiB on; csmp_tune(CSMP_TUNE_PIPELINES, 1) keeps one, 2 takes two whatever the size.
-    constexpr int64_t kPairMinSignals = 2;
-    constexpr size_t kPairMinBytes = (size_t)4 << 20;  // two pipelines: 1 MiB -10 %, 8 MiB +35 %, 32 MiB +40 %, 64 MiB ... 1 GiB +5 ... +16 %
-    csmp_ctx* tw = nullptr;
-    // (forward regression too: its ticks under the same LDS request -- one workgroup per CU -- 6.28e3 -> 6.57e3 atoms/s at the benchmark
-    // shape; without the request 6.47e3.  With the sweep body as round 5 left it the same pairing had measured 5.99e3 against 5.96e3.)
-    // ... and where a sweep is long enough for its tail to matter: dictionaries of kPairMinBytes and more (measured: tools/probes/
-    // pair_sizes.py); csmp_tune(CSMP_TUNE_PIPELINES, 2) takes two pipelines whatever the size
-    const size_t dict_bytes = (size_t)ctx->Mv * (size_t)ctx->N * (ctx->dtype == CSMP_F32 ? 4 : 8);
-    // GROUPED (omp only): each pipeline's three slots become three groups of up to sweep_group signals whose sweeps share one pass over
-    // A (omp_groups_pair).  csmp_tune(CSMP_TUNE_PIPELINES, 3) forces it; automatic wherever two pipelines run and a pass serves two or
-    // more signals.  Supports beyond qr_max_cols() (pipe), screened sweeps (csmp_omp_batch) and fr keep the schedules above.
-    const bool pair = pipe && nsig >= kPairMinSignals && ctx->tune_pipelines != 1 && (ctx->tune_pipelines >= 2 || dict_bytes >= kPairMinBytes);
-    const bool grouped = pair && !isfr && ctx->sweep_group >= 1 &&
-                         (ctx->tune_pipelines == 3 || (ctx->tune_pipelines == 0 && ctx->sweep_group >= 2));
-    if (pair) {
-        rc = twins_ensure(ctx, 1);
-        if (rc == CSMP_OK) {
+    const BatchSchedule sched = batch_schedule(ctx, isfr, nsig, kc);
+    const bool twin = sched == BatchSchedule::Pairs || sched == BatchSchedule::Grouped;
+    const int nslots = sched == BatchSchedule::Grouped ? 3 * ctx->sweep_group : 3;
+    csmp_ctx* tw = nullptr;  // pipeline B's context: a clone of this one on its own stream
+    auto ensure_slots = [&](csmp_ctx* c, int from) -> int {
+        int r2 = CSMP_OK;
+        for (int q = from; q < nslots && r2 == CSMP_OK; ++q) {
+            activate_slot(c, q);
+            r2 = solver_ensure(c, kc, (int)k);
+            if (r2 == CSMP_OK && isfr) r2 = fr_ensure(c);
+        }
+        activate_slot(c, 0);
+        return r2;
+    };
+    // f(context, signal) for every member of a round with its slot active: A's groups, then B's, group by group, member by member
+    auto each_member = [&](const PlanRound& r, auto&& f) -> int {
+        csmp_ctx* cs[2] = {ctx, tw};
+        for (int p = 0; p < 2; ++p)
+            for (int g = 0; g < 3; ++g)
+                for (int m = 0; m < r.g[p][g].size; ++m) {
+                    activate_slot(cs[p], g + 3 * m);
+                    const int r2 = f(cs[p], r.g[p][g].first + m);
+                    if (r2 != CSMP_OK) {
+                        if (cs[p] != ctx) ctx->err = cs[p]->err;
+                        return r2;
+                    }
+                }
+        return CSMP_OK;
+    };
+    auto run_plan = [&]() -> int {  // (every way out of here once the twin exists passes the drain below)
+        CHECK(ensure_slots(ctx, 1));
+        if (twin) {
+            CHECK(twins_ensure(ctx, 1));
             tw = ctx->twins[0];
             tw->prof = ctx->prof;  // (csmp_profile_*: the second pipeline's launches are sampled like the first's)
             tw->prof_every = ctx->prof_every;
-            for (int q = 0; q < 3 && rc == CSMP_OK; ++q) {
-                activate_slot(tw, q);
-                rc = solver_ensure(tw, kc, (int)k);
-                if (rc == CSMP_OK && isfr) rc = fr_ensure(tw);
+            const int r2 = ensure_slots(tw, 0);
+            if (r2 != CSMP_OK) {
+                ctx->err = tw->err;
+                return r2;
             }
-            activate_slot(tw, 0);
-            if (rc != CSMP_OK) ctx->err = tw->err;
-        }
-        if (rc == CSMP_OK && !ctx->ev_twin) HIPCHECK(hipEventCreateWithFlags(&ctx->ev_twin, hipEventDisableTiming));
-        if (rc == CSMP_OK && !tw->ev_twin) HIPCHECK(hipEventCreateWithFlags(&tw->ev_twin, hipEventDisableTiming));
-        if (rc == CSMP_OK) {  // (the twin starts behind everything this context's stream holds: the caller's buffers, the slots' allocation)
+            if (!ctx->ev_twin) HIPCHECK(hipEventCreateWithFlags(&ctx->ev_twin, hipEventDisableTiming));
+            if (!tw->ev_twin) HIPCHECK(hipEventCreateWithFlags(&tw->ev_twin, hipEventDisableTiming));
+            // (the twin starts behind everything this context's stream holds: the caller's buffers, the slots' allocation)
             HIPCHECK(hipEventRecord(ctx->ev_twin, ctx->stream));
             HIPCHECK(hipStreamWaitEvent(tw->stream, ctx->ev_twin, 0));
         }
-    }
-    if (pipe) {
-        for (int q = 1; q < 3 && rc == CSMP_OK; ++q) {
-            activate_slot(ctx, q);
-            rc = solver_ensure(ctx, kc, (int)k);
-            if (rc == CSMP_OK && isfr) rc = fr_ensure(ctx);
+        for (const PlanRound& r : batch_plan(nsig, sched, ctx->sweep_group)) {
+            CHECK(each_member(r, init));
+            CHECK(ctx->dtype == CSMP_F32 ? run_round<float>(r, ctx, tw, isfr, k, eps, p2) : run_round<double>(r, ctx, tw, isfr, k, eps, p2));
+            CHECK(each_member(r, finish));
         }
+        if (twin) {  // this context's stream goes on behind the twin's last launch
+            HIPCHECK(hipEventRecord(tw->ev_twin, tw->stream));
+            HIPCHECK(hipStreamWaitEvent(ctx->stream, tw->ev_twin, 0));
+        }
+        return CSMP_OK;
+    };
+    if (sched == BatchSchedule::Signals) {
+        for (int64_t sgn = 0; sgn < nsig && rc == CSMP_OK; ++sgn) rc = solve_one(sgn, true);
+    } else {
+        rc = run_plan();
         activate_slot(ctx, 0);
-        auto init_triple = [&](csmp_ctx* c, int64_t first, int64_t end, bool present[3]) -> int {
-            int r2 = CSMP_OK;
-            for (int q = 0; q < 3 && r2 == CSMP_OK; ++q) {
-                present[q] = first + q < end;
-                if (!present[q]) continue;
-                activate_slot(c, q);
-                const char* col = (const char*)dB + (size_t)(first + q) * (size_t)ldB * es;
-                r2 = b_dtype == CSMP_F32 ? init_from_device_t<float>(c, (const float*)col) : init_from_device_t<double>(c, (const double*)col);
-            }
-            if (r2 != CSMP_OK && c != ctx) ctx->err = c->err;
-            return r2;
-        };
-        auto finish_triple = [&](csmp_ctx* c, int64_t first, const bool present[3]) -> int {
-            int r2 = CSMP_OK;
-            for (int q = 0; q < 3 && r2 == CSMP_OK; ++q) {
-                if (!present[q]) continue;
-                activate_slot(c, q);
-                r2 = launch_finish(c, d_idx + (first + q) * k, d_val + (first + q) * k, d_nnz + first + q, nullptr, (int)k, sigflags + first + q);
-            }
-            activate_slot(c, 0);
-            if (r2 != CSMP_OK && c != ctx) ctx->err = c->err;
-            return r2;
-        };
-        auto ensure_slots = [&](csmp_ctx* c, int nslots) -> int {  // (slots 0..2 are ready: above)
-            int r2 = CSMP_OK;
-            for (int q = 3; q < nslots && r2 == CSMP_OK; ++q) {
-                activate_slot(c, q);
-                r2 = solver_ensure(c, kc, (int)k);
-            }
-            activate_slot(c, 0);
-            if (r2 != CSMP_OK && c != ctx) ctx->err = c->err;
-            return r2;
-        };
-        if (tw && grouped && rc == CSMP_OK) {
-            // the fewest shared passes: ceil(nsig / R) groups, their sizes as even as possible, dealt in rounds of six -- groups 0, 2, 4
-            // of a round to this context's pipeline, 1, 3, 5 to the twin's.  Member m of a pipeline's group g is its slot g + 3 m.
-            const int R = ctx->sweep_group;
-            const int64_t ngroups = (nsig + R - 1) / R;
-            const int64_t base = nsig / ngroups, extra = nsig % ngroups;
-            auto gsize = [&](int64_t i) { return (int)(base + (i < extra ? 1 : 0)); };
-            rc = ensure_slots(ctx, 3 * R);
-            if (rc == CSMP_OK) rc = ensure_slots(tw, 3 * R);
-            int64_t first = 0;
-            for (int64_t g0 = 0; g0 < ngroups && rc == CSMP_OK; g0 += 6) {
-                int sz[2][3] = {{0, 0, 0}, {0, 0, 0}};
-                int64_t gfirst[2][3] = {{0, 0, 0}, {0, 0, 0}};
-                csmp_ctx* cs[2] = {ctx, tw};
-                for (int64_t g = g0; g < std::min<int64_t>(g0 + 6, ngroups); ++g) {
-                    const int pl = (int)((g - g0) % 2), slot = (int)((g - g0) / 2);
-                    sz[pl][slot] = gsize(g);
-                    gfirst[pl][slot] = first;
-                    first += gsize(g);
-                }
-                for (int pl = 0; pl < 2 && rc == CSMP_OK; ++pl)
-                    for (int gg = 0; gg < 3 && rc == CSMP_OK; ++gg)
-                        for (int m = 0; m < sz[pl][gg] && rc == CSMP_OK; ++m) {
-                            csmp_ctx* c = cs[pl];
-                            activate_slot(c, gg + 3 * m);
-                            const char* col = (const char*)dB + (size_t)(gfirst[pl][gg] + m) * (size_t)ldB * es;
-                            rc = b_dtype == CSMP_F32 ? init_from_device_t<float>(c, (const float*)col) : init_from_device_t<double>(c, (const double*)col);
-                            if (rc != CSMP_OK && c != ctx) ctx->err = c->err;
-                        }
-                if (rc != CSMP_OK) break;
-                rc = ctx->dtype == CSMP_F32 ? omp_groups_pair<float>(ctx, sz[0], tw, sz[1], k, eps, opt, kPairTickGrid)
-                                            : omp_groups_pair<double>(ctx, sz[0], tw, sz[1], k, eps, opt, kPairTickGrid);
-                for (int pl = 0; pl < 2 && rc == CSMP_OK; ++pl) {
-                    for (int gg = 0; gg < 3 && rc == CSMP_OK; ++gg)
-                        for (int m = 0; m < sz[pl][gg] && rc == CSMP_OK; ++m) {
-                            csmp_ctx* c = cs[pl];
-                            const int64_t sg = gfirst[pl][gg] + m;
-                            activate_slot(c, gg + 3 * m);
-                            rc = launch_finish(c, d_idx + sg * k, d_val + sg * k, d_nnz + sg, nullptr, (int)k, sigflags + sg);
-                            if (rc != CSMP_OK && c != ctx) ctx->err = c->err;
-                        }
-                    activate_slot(cs[pl], 0);
-                }
-            }
-            sgn = nsig;
-            if (rc == CSMP_OK) {
-                HIPCHECK(hipEventRecord(tw->ev_twin, tw->stream));
-                HIPCHECK(hipStreamWaitEvent(ctx->stream, tw->ev_twin, 0));
-            } else {
-                (void)hipStreamSynchronize(tw->stream);
-                (void)hipStreamSynchronize(ctx->stream);
-            }
+        if (tw) activate_slot(tw, 0);
+        if (rc != CSMP_OK && tw) {  // (a failed enqueue: both streams drained before anything is released)
+            (void)hipStreamSynchronize(tw->stream);
+            (void)hipStreamSynchronize(ctx->stream);
         }
-        if (tw && !grouped && rc == CSMP_OK) {
-            // rounds of 3 + 3 signals (this context's pipeline + the twin's), then the remainder in rounds of 1 + 1 and a last lone
-            // signal: measured on the 1-GiB dictionary, atoms/s of a whole batch -- 3 + 3: 6680, 1 + 1: 6690, 2 + 2: 6486, and the
-            // rounds whose pipelines hold different numbers 3 + 2: 6340, 2 + 1: 6332 (one pipeline of three: 6306, a lone signal:
-            // 5830; tools/probes/few_signals.sh).  Two streams with a sweep ready each keep the HBM busy; what costs is a round in
-            // which one stream's ticks have sweeps the other's have not.
-            const size_t fr_pair_lds = (size_t)(ctx->tune_pair_lds_kib > 0 ? ctx->tune_pair_lds_kib : kPairLdsKiB) * 1024;
-            struct Round { int64_t fa; int ca; int64_t fb; int cb; };
-            std::vector<Round> rounds;
-            {
-                int64_t at = 0;
-                for (; nsig - at >= 6; at += 6) rounds.push_back({at, 3, at + 3, 3});
-                for (; nsig - at >= 2; at += 2) rounds.push_back({at, 1, at + 1, 1});
-                if (at < nsig) rounds.push_back({at, 1, 0, 0});
-            }
-            for (size_t j = 0; j < rounds.size() && rc == CSMP_OK; ++j) {
-                bool pa[3], pb[3];
-                const int64_t fa = rounds[j].fa, fb = rounds[j].fb;
-                const bool hasb = rounds[j].cb > 0;
-                rc = init_triple(ctx, fa, fa + rounds[j].ca, pa);
-                if (rc == CSMP_OK && hasb) rc = init_triple(tw, fb, fb + rounds[j].cb, pb);
-                if (rc != CSMP_OK) break;
-                if (hasb && isfr)
-                    rc = ctx->dtype == CSMP_F32 ? fr_ticks_pair<float>(ctx, pa, tw, pb, k, eps, p2, opt, fr_pair_lds)
-                                                : fr_ticks_pair<double>(ctx, pa, tw, pb, k, eps, p2, opt, fr_pair_lds);
-                else if (hasb)
-                    rc = ctx->dtype == CSMP_F32 ? omp_ticks_pair<float>(ctx, pa, tw, pb, k, eps, opt, kPairTickGrid)
-                                                : omp_ticks_pair<double>(ctx, pa, tw, pb, k, eps, opt, kPairTickGrid);
-                else if (isfr)
-                    rc = ctx->dtype == CSMP_F32 ? fr_ticks<float>(ctx, pa, k, eps, p2, opt) : fr_ticks<double>(ctx, pa, k, eps, p2, opt);
-                else
-                    rc = ctx->dtype == CSMP_F32 ? omp_ticks<float>(ctx, pa, k, eps, opt) : omp_ticks<double>(ctx, pa, k, eps, opt);
-                if (rc == CSMP_OK) rc = finish_triple(ctx, fa, pa);
-                if (rc == CSMP_OK && hasb) rc = finish_triple(tw, fb, pb);
-            }
-            sgn = nsig;
-            // this context's stream goes on behind the twin's last launch (a failed enqueue: drain both before anything is released)
-            if (rc == CSMP_OK) {
-                HIPCHECK(hipEventRecord(tw->ev_twin, tw->stream));
-                HIPCHECK(hipStreamWaitEvent(ctx->stream, tw->ev_twin, 0));
-            } else {
-                (void)hipStreamSynchronize(tw->stream);
-                (void)hipStreamSynchronize(ctx->stream);
-            }
-        }
-        for (; sgn < nsig && rc == CSMP_OK; sgn += 3) {
-            bool present[3];
-            rc = init_triple(ctx, sgn, nsig, present);
-            if (rc == CSMP_OK && isfr)
-                rc = ctx->dtype == CSMP_F32 ? fr_ticks<float>(ctx, present, k, eps, p2, opt) : fr_ticks<double>(ctx, present, k, eps, p2, opt);
-            else if (rc == CSMP_OK)
-                rc = ctx->dtype == CSMP_F32 ? omp_ticks<float>(ctx, present, k, eps, opt) : omp_ticks<double>(ctx, present, k, eps, opt);
-            if (rc == CSMP_OK) rc = finish_triple(ctx, sgn, present);
-        }
-        activate_slot(ctx, 0);
     }
-    for (; sgn < nsig && rc == CSMP_OK; ++sgn) rc = solve_one(sgn, opt);
     // ... then ONE synchronisation: a signal whose support failed the DGKS test (flagged on the
     // device, nothing committed for the failing column) is solved again with the full chain
     if (rc == CSMP_OK) {

@@ -160,28 +160,35 @@ def test_every_allocation_may_fail(cs, dtype):
     fam, y, B = _families(cs, L, A, eps)
     gc.collect()
     base = L.live_resources()
-    for name, f in sorted(fam.items()):
+    # (pipelines 2: the twin context's allocations are among those that fail in turn; omp_batch once more under the grouped scheduler,
+    # groups of two: the slots beyond the first three of both contexts fail in turn too)
+    cases = [(name, f, {"pipelines": 2}, 200) for name, f in sorted(fam.items())]
+    cases.append(("omp_batch", fam["omp_batch"], {"pipelines": 3, "group_max": 2}, 600))
+    for name, f, tunes, most in cases:
         clean = cs.Dictionary(A)
-        clean.ctx.tune("pipelines", 2)  # (the twin context's allocations are among those that fail in turn)
+        for key, v in tunes.items():
+            clean.ctx.tune(key, v)
+        assert clean.ctx.sweep_config()["group_max"] == tunes.get("group_max", clean.ctx.sweep_config()["group_max"])
         want = f(clean.ctx)
         clean.close()
         n, seen_ok = 0, 0
-        while seen_ok < 2 and n < 200:  # (two successes in a row: n is past every allocation of the call)
+        while seen_ok < 2 and n < most:  # (two successes in a row: n is past every allocation of the call)
             n += 1
             d = cs.Dictionary(A)
-            d.ctx.tune("pipelines", 2)
+            for key, v in tunes.items():
+                d.ctx.tune(key, v)
             d.ctx.tune("fail_alloc", n)
             try:
                 got = f(d.ctx)
-                assert _same(got, want), (name, n, "the call went through with a result of its own")
+                assert _same(got, want), (name, tunes, n, "the call went through with a result of its own")
                 seen_ok += 1
             except cs.CsmpError as e:
                 seen_ok = 0
-                assert e.code in (L.EHIP, L.ENOMEM), (name, n, e.code, str(e))
+                assert e.code in (L.EHIP, L.ENOMEM), (name, tunes, n, e.code, str(e))
             d.ctx.tune("fail_alloc", 0)
             got = f(d.ctx)
-            assert _same(got, want), (name, n, "after the failed call")
+            assert _same(got, want), (name, tunes, n, "after the failed call")
             d.close()
-        assert n < 200, name
+        assert n < most, (name, tunes)
     gc.collect()
     assert L.live_resources() == base

@@ -26,8 +26,8 @@ def signals(cs, A, k, nsig, seed):
 @pytest.mark.parametrize("cfg", [(256, 1024, 12, 6, np.float64), (256, 1024, 12, 7, np.float64), (1000, 3000, 9, 13, np.float32),
                                  (4096, 2500, 10, 12, np.float32), (2048, 1500, 8, 8, np.float64), (300, 700, 5, 17, np.float32)])
 def test_two_pipelines_give_the_bits_of_one(cs, oracle, cfg):
-    """csmp_omp_batch runs two pipelines side by side, the second on a twin context (host/omp.hpp: omp_ticks_pair), in rounds of 3 + 3
-    signals, then 1 + 1, then a lone one (host/forward.hpp).  Whole rounds only (6, 12), a lone last signal (7, 13), rounds of 1 + 1
+    """csmp_omp_batch runs two pipelines side by side, the second on a twin context (host/omp.hpp: pipe_ticks), in rounds of 3 + 3
+    signals, then 1 + 1, then a lone one (host/batch_plan.hpp).  Whole rounds only (6, 12), a lone last signal (7, 13), rounds of 1 + 1
     (8), both (17)."""
     n, m, k, nsig, dtype = cfg
     eps = float(np.finfo(dtype).eps)
@@ -54,7 +54,7 @@ def test_two_pipelines_give_the_bits_of_one(cs, oracle, cfg):
 
 @pytest.mark.parametrize("cfg", [(256, 1024, 10, 6, np.float64), (1024, 3000, 9, 7, np.float32), (512, 2048, 8, 11, np.float32), (256, 700, 6, 2, np.float64)])
 def test_two_pipelines_of_forward_regression_give_the_bits_of_one(cs, oracle, cfg):
-    """csmp_fr_batch side by side on a twin context (host/forward.hpp: fr_ticks_pair, the ticks under the one-workgroup-per-CU LDS
+    """csmp_fr_batch side by side on a twin context (host/forward.hpp: fr_pipe_launch, the ticks under the one-workgroup-per-CU LDS
     request): rounds of 3 + 3, 1 + 1 and a lone signal; supports, coefficients and counts of one pipeline bit for bit, and the oracle's
     forward regression (src/forward.jl:44-72)."""
     n, m, k, nsig, dtype = cfg

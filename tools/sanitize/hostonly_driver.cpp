@@ -1,7 +1,9 @@
 // tools/sanitize/hostonly_driver.cpp -- drives the context-free exports of include/csmp.h (host/hostonly.hpp: dictionary files, the
-// sharded gather's wire layout) under gcc's AddressSanitizer + UndefinedBehaviorSanitizer.  CPU only: no HIP, no GPU.
+// sharded gather's wire layout) and the round plans of the batch drivers (host/batch_plan.hpp) under gcc's AddressSanitizer +
+// UndefinedBehaviorSanitizer.  CPU only: no HIP, no GPU.
 // Built and run by tools/sanitize_cpu.sh; argv[1] = tests/golden (the committed dictionary files), argv[2] = a scratch directory.
 #include "../../compressedsensing.jl_amd/csrc/host/hostonly.hpp"
+#include "../../compressedsensing.jl_amd/csrc/host/batch_plan.hpp"
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -155,6 +157,97 @@ static void wire_layout() {
     EXPECT(csmp_unpack_results(p3, -1, 1, &i1, &v1, &n1) == CSMP_EINVAL);
 }
 
+// the stage rotation: group g's step t sweeps at tick 3t + g, runs its qr1 stage at 3t + g + 1 and its qr2 stage at 3t + g + 2, all
+// of it inside the 3k + 2 ticks of a round, and a group of size 0 is never live
+static void tick_rotation() {
+    for (int64_t k = 1; k <= 5; ++k)
+        for (int mask = 0; mask < 8; ++mask) {
+            const int size[3] = {mask & 1, (mask >> 1) & 1, 2 * ((mask >> 2) & 1)};
+            int stages[3][3] = {};  // [group][sweep, qr1, qr2]: live ticks
+            for (int64_t n = 0; n < 3 * k + 2; ++n) {
+                const TickStages t = tick_stages(n, k, size);
+                EXPECT(t.z == n % 3 && t.y == (n + 2) % 3 && t.x == (n + 1) % 3);
+                if (t.az) { EXPECT(n == 3 * t.tz + t.z && t.tz < k); stages[t.z][0] += 1; }
+                if (t.ay) stages[t.y][1] += 1;
+                if (t.ax) stages[t.x][2] += 1;
+                EXPECT(!t.ay || (n - 1 - t.y) % 3 == 0);
+                EXPECT(!t.ax || (n - 2 - t.x) % 3 == 0);
+            }
+            for (int g = 0; g < 3; ++g)
+                for (int st = 0; st < 3; ++st) EXPECT(stages[g][st] == (size[g] > 0 ? (int)k : 0));
+        }
+}
+
+// every plan of nsig 1..64 signals: each signal in exactly one (round, pipeline, group, member), the members of a group consecutive,
+// no solver slot at or above 3 * kGroupMax (= kSlots, host/ctx.hpp), and the round shapes of each schedule
+static void batch_plans() {
+    const int kSlots = 3 * 4;
+    for (int64_t nsig = 1; nsig <= 64; ++nsig)
+        for (int R = 1; R <= 4; ++R)
+            for (BatchSchedule sched : {BatchSchedule::Signals, BatchSchedule::One, BatchSchedule::Pairs, BatchSchedule::Grouped}) {
+                const std::vector<PlanRound> plan = batch_plan(nsig, sched, R);
+                if (sched == BatchSchedule::Signals) {
+                    EXPECT(plan.empty());
+                    continue;
+                }
+                std::vector<int> seen((size_t)nsig, 0);
+                int64_t next = 0;  // signals are dealt in order: A's groups, then B's, within a round
+                const int64_t ngroups = (nsig + R - 1) / R;
+                for (size_t j = 0; j < plan.size(); ++j) {
+                    const PlanRound& r = plan[j];
+                    int count[2] = {0, 0}, live[2] = {0, 0};
+                    for (int p = 0; p < 2; ++p)
+                        for (int g = 0; g < 3; ++g) {
+                            const PlanGroup& G = r.g[p][g];
+                            EXPECT(G.size >= 0);
+                            if (G.size == 0) continue;
+                            EXPECT(g + 3 * (G.size - 1) < kSlots);
+                            for (int m = 0; m < G.size; ++m) {
+                                EXPECT(G.first + m >= 0 && G.first + m < nsig);
+                                if (G.first + m >= 0 && G.first + m < nsig) seen[(size_t)(G.first + m)] += 1;
+                            }
+                            count[p] += G.size;
+                            live[p] += 1;
+                        }
+                    if (sched == BatchSchedule::One) {
+                        // rounds of three consecutive signals on A, the last one 1 or 2 when nsig is not a multiple of three
+                        EXPECT(r.form == RoundForm::One && count[1] == 0);
+                        EXPECT(count[0] == (int)std::min<int64_t>(3, nsig - 3 * (int64_t)j));
+                        for (int g = 0; g < count[0]; ++g) EXPECT(r.g[0][g].first == next + g && r.g[0][g].size == 1);
+                    } else if (sched == BatchSchedule::Pairs) {
+                        const int64_t left = nsig - next;
+                        if (left >= 6) {
+                            EXPECT(r.form == RoundForm::Pair && count[0] == 3 && count[1] == 3);
+                            for (int g = 0; g < 3; ++g) EXPECT(r.g[0][g].first == next + g && r.g[1][g].first == next + 3 + g);
+                        } else if (left >= 2) {
+                            EXPECT(r.form == RoundForm::Pair && count[0] == 1 && count[1] == 1);
+                            EXPECT(r.g[0][0].first == next && r.g[1][0].first == next + 1);
+                        } else {  // the lone last signal: the one-pipeline form
+                            EXPECT(j + 1 == plan.size() && r.form == RoundForm::One && count[0] == 1 && count[1] == 0);
+                            EXPECT(r.g[0][0].first == next);
+                        }
+                    } else {
+                        // six groups to a round (fewer in the last), dealt A, B, A, B, ... in slot order; a last round with no group on B
+                        // keeps the pair form
+                        EXPECT(r.form == RoundForm::Grouped);
+                        const int64_t in_round = std::min<int64_t>(6, ngroups - 6 * (int64_t)j);
+                        EXPECT(live[0] == (int)(in_round + 1) / 2 && live[1] == (int)in_round / 2);
+                        for (int64_t i = 0; i < in_round; ++i) {
+                            const PlanGroup& G = r.g[i % 2][i / 2];
+                            const int64_t gi = 6 * (int64_t)j + i;
+                            EXPECT(G.first == next && G.size == (int)(nsig / ngroups + (gi < nsig % ngroups ? 1 : 0)) && G.size <= R);
+                            next += G.size;
+                        }
+                        continue;
+                    }
+                    next += count[0] + count[1];
+                }
+                EXPECT(next == nsig);
+                if (sched == BatchSchedule::Grouped) EXPECT((int64_t)plan.size() == (ngroups + 5) / 6);
+                for (int64_t s = 0; s < nsig; ++s) EXPECT(seen[(size_t)s] == 1);
+            }
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <tests/golden> <scratch directory>\n", argv[0]);
@@ -163,6 +256,8 @@ int main(int argc, char** argv) {
     dictionary_files(argv[1], argv[2]);
     shard_ranges();
     wire_layout();
+    tick_rotation();
+    batch_plans();
     std::printf("hostonly_driver: %s (%d failed expectation(s))\n", fails ? "FAILED" : "ok", fails);
     return fails ? 1 : 0;
 }

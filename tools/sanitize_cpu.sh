@@ -6,7 +6,8 @@
 #   2. the same oracle as a sanitized shared object under the CPU test suites that exercise it (tests/test_oracle.py,
 #      tests/test_host.py; LD_PRELOAD of the sanitizer runtime, leak detection off: the interpreter's own allocations are not ours);
 #   3. the context-free exports of include/csmp.h (host/hostonly.hpp: dictionary files, the sharded gather's wire layout) as a
-#      host-only object driven by tools/sanitize/hostonly_driver.cpp over tests/golden/dict_*.csmp.
+#      host-only object driven by tools/sanitize/hostonly_driver.cpp over tests/golden/dict_*.csmp, and the batch drivers' round
+#      plans and tick rotation (host/batch_plan.hpp).
 # Exit status 0 = every part ran clean.  Usage: tools/sanitize_cpu.sh [log file]   (default: profiles/r06_sanitize_cpu.txt)
 set -u
 cd "$(dirname "$0")/.."
@@ -41,9 +42,9 @@ step "2b. run: tests/test_oracle.py + tests/test_host.py against it (CSMP_ORACLE
         python -m pytest tests/test_oracle.py tests/test_host.py -q -m "not gpu" -p no:cacheprovider
 
 mkdir -p "$OUT/scratch"
-step "3a. build: the context-free exports (host/hostonly.hpp) + their driver, sanitized" \
+step "3a. build: the context-free exports (host/hostonly.hpp), the batch round plans (host/batch_plan.hpp) + their driver, sanitized" \
     g++ -std=c++17 -O1 $SAN -Wall -Wextra -o "$OUT/hostonly_driver" tools/sanitize/hostonly_driver.cpp
-step "3b. run: dictionary files (tests/golden/dict_*.csmp, damaged copies, bad arguments), shard ranges, the gather's wire layout" \
+step "3b. run: dictionary files (tests/golden/dict_*.csmp, damaged copies, bad arguments), shard ranges, the gather's wire layout, batch round plans" \
     env ASAN_OPTIONS=detect_leaks=1:abort_on_error=0 UBSAN_OPTIONS=print_stacktrace=1 "$OUT/hostonly_driver" tests/golden "$OUT/scratch"
 
 echo "== result: $([ $status -eq 0 ] && echo 'all parts clean' || echo 'FAILURES above')" | tee -a "$LOG"
