@@ -423,114 +423,71 @@ class Context:
         self.call("csmp_fr_scores", ptr(d2))
         return d2
 
-    def omp_batch(self, B, k, eps):
-        """Host matrix B (M x nsig, column-major) -> (idx k x nsig, val, nnz) numpy arrays."""
+    def _batch_host(self, name, B, k, args, locs=True):
+        """The batch entry `name` on the host matrix B (M x nsig, column-major) -> (idx k x nsig, val, nnz) numpy arrays, + iters for
+        csmp_sp_batch (locs False: no b_loc / out_loc arguments).  args: those between nsig (b_loc) and the outputs."""
         B = np.asfortranarray(B)
         if B.dtype not in (np.float32, np.float64):
             B = B.astype(np.float64)
         M, nsig = B.shape
         if M != self.M:
             raise CsmpError(EDIM, f"size(B, 1) = {M} but size(A, 1) = {self.M}")
-        idx = np.zeros((int(k), nsig), np.int64, order="F")
-        val = np.zeros((int(k), nsig), np.float64, order="F")
-        nnz = np.zeros(nsig, np.int64)
-        self.call("csmp_omp_batch", ptr(B), dtype_code(B.dtype), i64(M), i64(nsig), HOST, i64(int(k)),
-                  C.c_double(eps), ptr(idx), ptr(val), ptr(nnz), HOST)
-        return idx, val, nnz
+        out = (np.zeros((int(k), nsig), np.int64, order="F"), np.zeros((int(k), nsig), np.float64, order="F"), np.zeros(nsig, np.int64))
+        if locs:
+            self.call(name, ptr(B), dtype_code(B.dtype), i64(M), i64(nsig), HOST, *args, *map(ptr, out), HOST)
+            return out
+        out += (np.zeros(nsig, np.int64),)
+        self.call(name, ptr(B), dtype_code(B.dtype), i64(M), i64(nsig), *args, *map(ptr, out))
+        return out
+
+    def _batch_device(self, name, B, k, args, idx, val, nnz):
+        """The batch entry `name` on torch CUDA tensors: B (nsig, M) rows = signals; outputs idx (nsig, k) int64, val (nsig, k) float64,
+        nnz (nsig,) int64.  args: those between b_loc and the outputs."""
+        import torch
+        nsig, M = B.shape
+        assert B.is_cuda and B.is_contiguous() and M == self.M
+        assert idx.dtype == torch.int64 and val.dtype == torch.float64 and nnz.dtype == torch.int64
+        assert idx.is_contiguous() and val.is_contiguous() and idx.shape == (nsig, int(k)) and val.shape == (nsig, int(k))
+        code = F32 if B.dtype == torch.float32 else F64
+        self.call(name, vp(B.data_ptr()), code, i64(M), i64(nsig), DEVICE, *args, vp(idx.data_ptr()), vp(val.data_ptr()),
+                  vp(nnz.data_ptr()), DEVICE)
+
+    def omp_batch(self, B, k, eps):
+        """Host matrix B (M x nsig, column-major) -> (idx k x nsig, val, nnz) numpy arrays."""
+        return self._batch_host("csmp_omp_batch", B, k, (i64(int(k)), C.c_double(eps)))
+
+    def omp_batch_device(self, B, k, eps, idx, val, nnz):
+        """torch CUDA tensors: B (nsig, M) rows = signals; outputs idx (nsig, k) int64,
+        val (nsig, k) float64, nnz (nsig,) int64.  Only enqueues work; call sync()."""
+        self._batch_device("csmp_omp_batch", B, k, (i64(int(k)), C.c_double(eps)), idx, val, nnz)
 
     def gomp_batch(self, B, l, k, eps):
         """Host matrix B (M x nsig, column-major) -> (idx k x nsig, val, nnz): gomp for every column, two solves in flight."""
-        B = np.asfortranarray(B)
-        if B.dtype not in (np.float32, np.float64):
-            B = B.astype(np.float64)
-        M, nsig = B.shape
-        if M != self.M:
-            raise CsmpError(EDIM, f"size(B, 1) = {M} but size(A, 1) = {self.M}")
-        idx = np.zeros((int(k), nsig), np.int64, order="F")
-        val = np.zeros((int(k), nsig), np.float64, order="F")
-        nnz = np.zeros(nsig, np.int64)
-        self.call("csmp_gomp_batch", ptr(B), dtype_code(B.dtype), i64(M), i64(nsig), HOST, i64(int(l)), i64(int(k)),
-                  C.c_double(eps), ptr(idx), ptr(val), ptr(nnz), HOST)
-        return idx, val, nnz
+        return self._batch_host("csmp_gomp_batch", B, k, (i64(int(l)), i64(int(k)), C.c_double(eps)))
 
     def gomp_batch_device(self, B, l, k, eps, idx, val, nnz):
-        """torch CUDA tensors: B (nsig, M) rows = signals; outputs idx (nsig, k) int64, val (nsig, k) float64, nnz (nsig,) int64."""
-        import torch
-        nsig, M = B.shape
-        assert B.is_cuda and B.is_contiguous() and M == self.M
-        assert idx.dtype == torch.int64 and val.dtype == torch.float64 and nnz.dtype == torch.int64
-        assert idx.is_contiguous() and val.is_contiguous() and idx.shape == (nsig, int(k)) and val.shape == (nsig, int(k))
-        code = F32 if B.dtype == torch.float32 else F64
-        self.call("csmp_gomp_batch", vp(B.data_ptr()), code, i64(M), i64(nsig), DEVICE, i64(int(l)), i64(int(k)), C.c_double(eps),
-                  vp(idx.data_ptr()), vp(val.data_ptr()), vp(nnz.data_ptr()), DEVICE)
+        """torch CUDA tensors as in omp_batch_device."""
+        self._batch_device("csmp_gomp_batch", B, k, (i64(int(l)), i64(int(k)), C.c_double(eps)), idx, val, nnz)
 
     def sp_batch(self, B, k, delta=1e-12, maxiter=-1):
         """Host matrix B (M x nsig, column-major) -> (idx k x nsig, val, nnz, iters): sp for every column, several solves in flight."""
-        B = np.asfortranarray(B)
-        if B.dtype not in (np.float32, np.float64):
-            B = B.astype(np.float64)
-        M, nsig = B.shape
-        if M != self.M:
-            raise CsmpError(EDIM, f"size(B, 1) = {M} but size(A, 1) = {self.M}")
-        idx = np.zeros((int(k), nsig), np.int64, order="F")
-        val = np.zeros((int(k), nsig), np.float64, order="F")
-        nnz = np.zeros(nsig, np.int64)
-        its = np.zeros(nsig, np.int64)
-        self.call("csmp_sp_batch", ptr(B), dtype_code(B.dtype), i64(M), i64(nsig), i64(int(k)), C.c_double(delta), i64(int(maxiter)),
-                  ptr(idx), ptr(val), ptr(nnz), ptr(its))
-        return idx, val, nnz, its
+        return self._batch_host("csmp_sp_batch", B, k, (i64(int(k)), C.c_double(delta), i64(int(maxiter))), locs=False)
 
     def fr_batch(self, B, k, max_eps=0.0, min_delta=0.0):
         """fr for every column of the host matrix B (M x nsig, column-major) -> (idx k x nsig, val, nnz)."""
-        B = np.asfortranarray(B)
-        if B.dtype not in (np.float32, np.float64):
-            B = B.astype(np.float64)
-        M, nsig = B.shape
-        if M != self.M:
-            raise CsmpError(EDIM, f"size(B, 1) = {M} but size(A, 1) = {self.M}")
-        idx = np.zeros((int(k), nsig), np.int64, order="F")
-        val = np.zeros((int(k), nsig), np.float64, order="F")
-        nnz = np.zeros(nsig, np.int64)
-        self.call("csmp_fr_batch", ptr(B), dtype_code(B.dtype), i64(M), i64(nsig), HOST, i64(int(k)),
-                  C.c_double(max_eps), C.c_double(min_delta), ptr(idx), ptr(val), ptr(nnz), HOST)
-        return idx, val, nnz
+        return self._batch_host("csmp_fr_batch", B, k, (i64(int(k)), C.c_double(max_eps), C.c_double(min_delta)))
 
     def fr_batch_device(self, B, k, max_eps, min_delta, idx, val, nnz):
         """torch CUDA tensors as in omp_batch_device.  Only enqueues work; call sync()."""
-        import torch
-        nsig, M = B.shape
-        assert B.is_cuda and B.is_contiguous() and M == self.M
-        assert idx.dtype == torch.int64 and val.dtype == torch.float64 and nnz.dtype == torch.int64
-        assert idx.is_contiguous() and val.is_contiguous() and idx.shape == (nsig, int(k)) and val.shape == (nsig, int(k))
-        code = F32 if B.dtype == torch.float32 else F64
-        self.call("csmp_fr_batch", vp(B.data_ptr()), code, i64(M), i64(nsig), DEVICE, i64(int(k)), C.c_double(max_eps),
-                  C.c_double(min_delta), vp(idx.data_ptr()), vp(val.data_ptr()), vp(nnz.data_ptr()), DEVICE)
+        self._batch_device("csmp_fr_batch", B, k, (i64(int(k)), C.c_double(max_eps), C.c_double(min_delta)), idx, val, nnz)
 
     def omp_batch_mfma(self, B, k, eps):
         """Batched (MFMA-screened) variant of omp_batch: same inputs and outputs."""
-        B = np.asfortranarray(B)
-        if B.dtype not in (np.float32, np.float64):
-            B = B.astype(np.float64)
-        M, nsig = B.shape
-        if M != self.M:
-            raise CsmpError(EDIM, f"size(B, 1) = {M} but size(A, 1) = {self.M}")
-        idx = np.zeros((int(k), nsig), np.int64, order="F")
-        val = np.zeros((int(k), nsig), np.float64, order="F")
-        nnz = np.zeros(nsig, np.int64)
-        self.call("csmp_omp_batch_mfma", ptr(B), dtype_code(B.dtype), i64(M), i64(nsig), HOST, i64(int(k)),
-                  C.c_double(eps), ptr(idx), ptr(val), ptr(nnz), HOST)
-        return idx, val, nnz
+        return self._batch_host("csmp_omp_batch_mfma", B, k, (i64(int(k)), C.c_double(eps)))
 
     def omp_batch_mfma_device(self, B, k, eps, idx, val, nnz):
         """torch CUDA tensors as in omp_batch_device; synchronises once at the end."""
-        import torch
-        nsig, M = B.shape
-        assert B.is_cuda and B.is_contiguous() and M == self.M
-        assert idx.dtype == torch.int64 and val.dtype == torch.float64 and nnz.dtype == torch.int64
-        assert idx.is_contiguous() and val.is_contiguous() and idx.shape == (nsig, int(k)) and val.shape == (nsig, int(k))
-        code = F32 if B.dtype == torch.float32 else F64
-        self.call("csmp_omp_batch_mfma", vp(B.data_ptr()), code, i64(M), i64(nsig), DEVICE, i64(int(k)), C.c_double(eps),
-                  vp(idx.data_ptr()), vp(val.data_ptr()), vp(nnz.data_ptr()), DEVICE)
+        self._batch_device("csmp_omp_batch_mfma", B, k, (i64(int(k)), C.c_double(eps)), idx, val, nnz)
 
     def batch_screen_kernel(self):
         return lib().csmp_batch_screen_kernel(self._h).decode()
@@ -606,18 +563,6 @@ class Context:
         a, b = i64(0), i64(0)
         self.call("csmp_screened_stats", C.byref(a), C.byref(b), int(bool(reset)))
         return {"solves": a.value, "fallbacks": b.value}
-
-    def omp_batch_device(self, B, k, eps, idx, val, nnz):
-        """torch CUDA tensors: B (nsig, M) rows = signals; outputs idx (nsig, k) int64,
-        val (nsig, k) float64, nnz (nsig,) int64.  Only enqueues work; call sync()."""
-        import torch
-        nsig, M = B.shape
-        assert B.is_cuda and B.is_contiguous() and M == self.M
-        assert idx.dtype == torch.int64 and val.dtype == torch.float64 and nnz.dtype == torch.int64
-        assert idx.is_contiguous() and val.is_contiguous() and idx.shape == (nsig, int(k)) and val.shape == (nsig, int(k))
-        code = F32 if B.dtype == torch.float32 else F64
-        self.call("csmp_omp_batch", vp(B.data_ptr()), code, i64(M), i64(nsig), DEVICE, i64(int(k)), C.c_double(eps),
-                  vp(idx.data_ptr()), vp(val.data_ptr()), vp(nnz.data_ptr()), DEVICE)
 
     # ---- step level
     def solver_begin(self, algo, b, kcap, idx0=None, val0=None):

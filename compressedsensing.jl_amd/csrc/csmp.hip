@@ -39,6 +39,7 @@ using namespace csmp;
 #include "host/lifetime.hpp"
 #include "host/dictionary.hpp"
 #include "host/chain.hpp"
+#include "host/batch_io.hpp"
 #include "host/omp.hpp"
 #include "host/forward.hpp"
 #include "host/steps_sharding.hpp"

@@ -1,0 +1,134 @@
+// host/batch_io.hpp -- part of the host side of libcsmp.so (included by csmp.hip, in order; ONE translation unit):
+// the front end of the batch drivers (csmp_omp_batch, csmp_fr_batch, csmp_gomp_batch, csmp_sp_batch, csmp_omp_batch_mfma): the
+// checks they share, B and the outputs of a host caller on the device, the staggered schedule of whole solves on several
+// contexts, and the re-solve of one signal.
+// ------------------------------------------------------------------------------------------ batch front end
+// The arguments of one batch call (B: ldB x nsig column-major, idx / val: k x nsig, nnz: nsig) and the device copies a host
+// caller's B and outputs need.  Every temporary is freed on every return path.
+struct BatchIO {
+    csmp_ctx* ctx;
+    const void* B;
+    int b_dtype;
+    int64_t ldB, nsig;
+    int b_loc;
+    int64_t k;
+    int64_t* idx;
+    double* val;
+    int64_t* nnz;
+    int out_loc;
+    const char* dB;  // B where the solvers read it: on the device once stage() has run
+    int64_t *d_idx, *d_nnz;  // the outputs on the device
+    double* d_val;
+    int* d_flag = nullptr;  // per-signal stop flags: stage(true)
+    DevTmp tB, tIdx, tVal, tNnz, tFlag;
+
+    BatchIO(csmp_ctx* c, const void* B_, int b_dtype_, int64_t ldB_, int64_t nsig_, int b_loc_, int64_t k_, int64_t* idx_, double* val_,
+            int64_t* nnz_, int out_loc_)
+        : ctx(c), B(B_), b_dtype(b_dtype_), ldB(ldB_), nsig(nsig_), b_loc(b_loc_), k(k_), idx(idx_), val(val_), nnz(nnz_), out_loc(out_loc_),
+          dB((const char*)B_), d_idx(idx_), d_nnz(nnz_), d_val(val_) {}
+    BatchIO(const BatchIO&) = delete;
+    BatchIO& operator=(const BatchIO&) = delete;
+
+    size_t es() const { return b_dtype == CSMP_F32 ? 4 : 8; }
+    // signals off .. off+n of this call, unstaged (csmp_omp_batch_mfma's chunks)
+    BatchIO part(int64_t off, int64_t n) const {
+        return BatchIO(ctx, (const char*)B + (size_t)off * (size_t)ldB * es(), b_dtype, ldB, n, b_loc, k, idx + off * k, val + off * k,
+                       nnz + off, out_loc);
+    }
+    // The checks every batch entry shares.  An entry makes its own (eps, l, NaN tolerances, ...) before these, so that a bad
+    // argument is reported ahead of a missing dictionary, and those that depend on the dictionary's shape (2k > M) after them.
+    int check() const {
+        if ((b_loc != CSMP_HOST && b_loc != CSMP_DEVICE) || (out_loc != CSMP_HOST && out_loc != CSMP_DEVICE))
+            return fail(ctx, CSMP_EINVAL, "b_loc / out_loc must be CSMP_HOST or CSMP_DEVICE");
+        if (!B || nsig < 0 || k < 1 || ldB < ctx->M || (nsig > 0 && (!idx || !val || !nnz))) return fail(ctx, CSMP_EINVAL, "batch: bad arguments");
+        if (b_dtype != CSMP_F32 && b_dtype != CSMP_F64) return fail(ctx, CSMP_EINVAL, "b_dtype must be CSMP_F32 or CSMP_F64");
+        if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
+        return CSMP_OK;
+    }
+    // a host B to the device, device outputs for a host caller, and (flags) a stop-flag word per signal
+    int stage(bool flags) {
+        if (b_loc == CSMP_HOST) {
+            CHECK(tB.alloc(ctx, (size_t)ldB * (size_t)nsig * es()));
+            HIPCHECK(hipMemcpy(tB.p, B, (size_t)ldB * (size_t)nsig * es(), hipMemcpyHostToDevice));
+            dB = (const char*)tB.p;
+        }
+        if (out_loc == CSMP_HOST) {
+            CHECK(tIdx.alloc(ctx, (size_t)k * nsig * 8));
+            CHECK(tVal.alloc(ctx, (size_t)k * nsig * 8));
+            CHECK(tNnz.alloc(ctx, (size_t)nsig * 8));
+            d_idx = (int64_t*)tIdx.p;
+            d_val = (double*)tVal.p;
+            d_nnz = (int64_t*)tNnz.p;
+        }
+        if (flags) {
+            CHECK(tFlag.alloc(ctx, (size_t)nsig * sizeof(int)));
+            d_flag = (int*)tFlag.p;
+        }
+        return CSMP_OK;
+    }
+    const void* col(int64_t s) const { return dB + (size_t)s * (size_t)ldB * es(); }
+    int* flag(int64_t s) const { return d_flag + s; }
+    // signal s into c's active slot
+    int init(csmp_ctx* c, int64_t s) const {
+        return b_dtype == CSMP_F32 ? init_from_device_t<float>(c, (const float*)col(s)) : init_from_device_t<double>(c, (const double*)col(s));
+    }
+    // c's solution into signal s's outputs (sflag: its stop flags, or null)
+    int emit(csmp_ctx* c, int64_t s, int* sflag) const { return launch_finish(c, d_idx + s * k, d_val + s * k, d_nnz + s, nullptr, (int)k, sflag); }
+    // the end of the call: a host caller's outputs come back (after a success only), and this context's stream is drained
+    int done(int rc) {
+        if (out_loc == CSMP_HOST) {
+            if (rc == CSMP_OK) {
+                HIPCHECK(hipMemcpyAsync(idx, d_idx, (size_t)k * nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHECK(hipMemcpyAsync(val, d_val, (size_t)k * nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHECK(hipMemcpyAsync(nnz, d_nnz, (size_t)nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
+            }
+            HIPCHECK(hipStreamSynchronize(ctx->stream));
+        }
+        return rc;
+    }
+};
+
+// Signal s solved on c's active slot: its column in, step(t) for t = 0 .. k-1, the solution out
+template <typename Step>
+static int batch_solve(csmp_ctx* c, const BatchIO& io, int64_t s, int* flag, Step&& step) {
+    int rc = io.init(c, s);
+    for (int64_t t = 0; t < io.k && rc == CSMP_OK; ++t) rc = step(t);
+    return rc == CSMP_OK ? io.emit(c, s, flag) : rc;
+}
+// The exact re-solve of a signal some faster path flagged: omp with the full append chain
+static int omp_solve_exact(csmp_ctx* c, const BatchIO& io, int64_t s, double eps, int* flag) {
+    return batch_solve(c, io, s, flag, [&](int64_t t) { return omp_step(c, eps, t > 0, false); });
+}
+
+// The staggered schedule: T whole solves in flight on cc[0 .. T) -- a context and T - 1 twins, each on its own stream -- with
+// signal s on cc[s % T], everything enqueued up front.  enqueue(c, s, ev) enqueues signal s's solve on c and, when ev is not null,
+// records ev behind the solve's first sweep; the next twin's first solve waits for it.  The chains then run OUT of phase: one
+// signal's short stages fall under another's sweep (in phase they would fall on each other).  Returns once the twins' streams
+// are done; on a failure every stream is drained before the return.
+template <typename Enqueue>
+static int batch_stagger(csmp_ctx* const* cc, int T, int64_t nsig, Enqueue&& enqueue) {
+    csmp_ctx* ctx = cc[0];
+    auto run = [&]() -> int {
+        HIPCHECK(hipStreamSynchronize(ctx->stream));  // (the caller's buffers and our temporaries are ready before any stream starts)
+        for (int q = 0; q + 1 < T; ++q)
+            if (!cc[q]->ev_twin) HIPCHECK(hipEventCreateWithFlags(&cc[q]->ev_twin, hipEventDisableTiming));
+        for (int64_t s = 0; s < nsig; ++s) {
+            const int q = (int)(s % T);
+            csmp_ctx* c = cc[q];
+            if (s > 0 && s < T) HIPCHECK(hipStreamWaitEvent(c->stream, cc[q - 1]->ev_twin, 0));  // a twin starts one sweep behind
+            const int rc = enqueue(c, s, s + 1 < T ? c->ev_twin : nullptr);
+            if (rc != CSMP_OK) {
+                if (c != ctx) ctx->err = c->err;
+                return rc;
+            }
+        }
+        for (int w = 1; w < T; ++w) HIPCHECK(hipStreamSynchronize(cc[w]->stream));
+        return CSMP_OK;
+    };
+    const int rc = run();
+    if (rc != CSMP_OK)
+        for (int w = 0; w < T; ++w) (void)hipStreamSynchronize(cc[w]->stream);
+    return rc;
+}
+
+static int omp_batch_screened(csmp_ctx* ctx, BatchIO& io, double eps);  // host/screened.hpp

@@ -286,8 +286,7 @@ static size_t batch_bytes_per_signal(const csmp_ctx* ctx, int kc) {
            (size_t)b.n_atiles * kTileCand * 8 + (size_t)std::max<int64_t>(512, ((ctx->M + 255) / 256) * 256) + 4;
 }
 
-static int omp_batch_mfma_chunk(csmp_ctx* ctx, const void* B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k,
-                                double eps, int64_t* idx, double* val, int64_t* nnz, int out_loc);
+static int omp_batch_mfma_chunk(csmp_ctx* ctx, BatchIO& io, double eps);
 
 // The entry point: argument checks, then the batch in as many pieces as the free HBM asks for.  The per-signal state is dominated
 // by the two k x k Float64 factors (T = R^-1 and its transpose): 1024 signals at k = 128 hold 0.27 GB, at k = 2048 69 GB.  A batch
@@ -296,12 +295,10 @@ static int omp_batch_mfma_chunk(csmp_ctx* ctx, const void* B, int b_dtype, int64
 extern "C" int csmp_omp_batch_mfma(csmp_ctx* ctx, const void* B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k,
                                    double eps, int64_t* idx, double* val, int64_t* nnz, int out_loc) {
     if (!ctx) return CSMP_EINVAL;
-    if ((b_loc != CSMP_HOST && b_loc != CSMP_DEVICE) || (out_loc != CSMP_HOST && out_loc != CSMP_DEVICE))
-        return fail(ctx, CSMP_EINVAL, "b_loc / out_loc must be CSMP_HOST or CSMP_DEVICE");
     if (!(eps >= 0.0)) return fail(ctx, CSMP_EINVAL, "eps has to be non-negative");
-    if (!B || nsig < 1 || k < 1 || ldB < ctx->M) return fail(ctx, CSMP_EINVAL, "omp_batch_mfma: bad arguments");
-    if (b_dtype != CSMP_F32 && b_dtype != CSMP_F64) return fail(ctx, CSMP_EINVAL, "b_dtype must be CSMP_F32 or CSMP_F64");
-    if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
+    if (nsig < 1) return fail(ctx, CSMP_EINVAL, "omp_batch_mfma: bad arguments");
+    BatchIO io(ctx, B, b_dtype, ldB, nsig, b_loc, k, idx, val, nnz, out_loc);
+    CHECK(io.check());
     HIPCHECK(hipSetDevice(ctx->dev));
     Batch& b = ctx->bt;
     const int kc = (int)std::max<int64_t>(1, std::min<int64_t>(k, ctx->M));
@@ -328,12 +325,10 @@ extern "C" int csmp_omp_batch_mfma(csmp_ctx* ctx, const void* B, int b_dtype, in
                 return csmp_omp_batch(ctx, B, b_dtype, ldB, nsig, b_loc, k, eps, idx, val, nnz, out_loc);
             }
             if (fit < Bpad) {
-                const size_t es = b_dtype == CSMP_F32 ? 4 : 8;
                 int64_t tot_res = 0, tot_unc = 0, tot_ill = 0;
                 for (int64_t off = 0; off < nsig; off += fit) {
-                    const int64_t n = std::min<int64_t>(fit, nsig - off);
-                    CHECK(omp_batch_mfma_chunk(ctx, (const char*)B + (size_t)off * (size_t)ldB * es, b_dtype, ldB, n, b_loc, k, eps, idx + off * k,
-                                               val + off * k, nnz + off, out_loc));
+                    BatchIO part = io.part(off, std::min<int64_t>(fit, nsig - off));
+                    CHECK(omp_batch_mfma_chunk(ctx, part, eps));
                     tot_res += b.last_resolved;
                     tot_unc += b.last_uncertain;
                     tot_ill += b.last_illcond;
@@ -346,16 +341,12 @@ extern "C" int csmp_omp_batch_mfma(csmp_ctx* ctx, const void* B, int b_dtype, in
             }
         }
     }
-    return omp_batch_mfma_chunk(ctx, B, b_dtype, ldB, nsig, b_loc, k, eps, idx, val, nnz, out_loc);
+    return omp_batch_mfma_chunk(ctx, io, eps);
 }
 
-static int omp_batch_mfma_chunk(csmp_ctx* ctx, const void* B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k,
-                                double eps, int64_t* idx, double* val, int64_t* nnz, int out_loc) {
-    if (!ctx) return CSMP_EINVAL;
-    if (!(eps >= 0.0)) return fail(ctx, CSMP_EINVAL, "eps has to be non-negative");
-    if (!B || nsig < 1 || k < 1 || ldB < ctx->M) return fail(ctx, CSMP_EINVAL, "omp_batch_mfma: bad arguments");
-    if (b_dtype != CSMP_F32 && b_dtype != CSMP_F64) return fail(ctx, CSMP_EINVAL, "b_dtype must be CSMP_F32 or CSMP_F64");
-    if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
+// one batch of at most 2^20 signals whose per-signal state fits (the entry's checks made)
+static int omp_batch_mfma_chunk(csmp_ctx* ctx, BatchIO& io, double eps) {
+    const int64_t nsig = io.nsig, k = io.k;
     if (nsig > (1 << 20)) return fail(ctx, CSMP_ERANGE, "omp_batch_mfma: too many signals in one call");
     HIPCHECK(hipSetDevice(ctx->dev));
     const int kc0 = (int)std::max<int64_t>(1, std::min<int64_t>(k, ctx->M));
@@ -370,7 +361,7 @@ static int omp_batch_mfma_chunk(csmp_ctx* ctx, const void* B, int b_dtype, int64
         b0.last_screen_signals = 0;
         b0.last_signals = nsig;
         b0.last_resolved = b0.last_uncertain = b0.last_illcond = 0;
-        return csmp_omp_batch(ctx, B, b_dtype, ldB, nsig, b_loc, k, eps, idx, val, nnz, out_loc);
+        return csmp_omp_batch(ctx, io.B, io.b_dtype, io.ldB, nsig, io.b_loc, k, eps, io.idx, io.val, io.nnz, io.out_loc);
     }
     const int kc = (int)std::max<int64_t>(1, std::min<int64_t>(k, ctx->M));
     // Operands of the screen (CSMP_OPT_BATCH_SCREEN).  3 (default): binary16 images -- eleven significand bits: the rigorous bound is
@@ -389,30 +380,13 @@ static int omp_batch_mfma_chunk(csmp_ctx* ctx, const void* B, int b_dtype, int64
     Batch& b = ctx->bt;
     const bool gram = ctx->opt_batch_gram != 0;
     if (gram) CHECK(batch_gram(ctx));
-    const size_t es = b_dtype == CSMP_F32 ? 4 : 8;
-    void* dB = const_cast<void*>(B);
-    DevTmp tB, tIdx, tVal, tNnz;  // freed on every return path
-    if (b_loc == CSMP_HOST) {
-        HIPCHECK(tB.alloc((size_t)ldB * (size_t)nsig * es));
-        dB = tB.p;
-        HIPCHECK(hipMemcpy(dB, B, (size_t)ldB * (size_t)nsig * es, hipMemcpyHostToDevice));
-    }
-    int64_t *d_idx = idx, *d_nnz = nnz;
-    double* d_val = val;
-    if (out_loc == CSMP_HOST) {
-        HIPCHECK(tIdx.alloc((size_t)k * nsig * 8));
-        HIPCHECK(tVal.alloc((size_t)k * nsig * 8));
-        HIPCHECK(tNnz.alloc((size_t)nsig * 8));
-        d_idx = (int64_t*)tIdx.p;
-        d_val = (double*)tVal.p;
-        d_nnz = (int64_t*)tNnz.p;
-    }
+    CHECK(io.stage(false));
     const int Bpad = (int)(((nsig + 2 * kBT - 1) / (2 * kBT)) * (2 * kBT));  // whole 256-signal tiles
-    if (b_dtype == CSMP_F32)
-        hipLaunchKernelGGL(k_b_init<float>, dim3(Bpad), dim3(256), 0, ctx->stream, (const float*)dB, ldB, (int)ctx->M, (int)nsig, b.r, b.b, b.Mr, b.Rb, b.Mk, b.bs,
+    if (io.b_dtype == CSMP_F32)
+        hipLaunchKernelGGL(k_b_init<float>, dim3(Bpad), dim3(256), 0, ctx->stream, (const float*)io.dB, io.ldB, (int)ctx->M, (int)nsig, b.r, b.b, b.Mr, b.Rb, b.Mk, b.bs,
                            i8 ? b.R8 : (signed char*)nullptr, b.Mk8, b.sigscale, img == kOpF16 ? 1.0f / b.ascale16 : b.astep, img);
     else
-        hipLaunchKernelGGL(k_b_init<double>, dim3(Bpad), dim3(256), 0, ctx->stream, (const double*)dB, ldB, (int)ctx->M, (int)nsig, b.r, b.b, b.Mr, b.Rb, b.Mk, b.bs,
+        hipLaunchKernelGGL(k_b_init<double>, dim3(Bpad), dim3(256), 0, ctx->stream, (const double*)io.dB, io.ldB, (int)ctx->M, (int)nsig, b.r, b.b, b.Mr, b.Rb, b.Mk, b.bs,
                            i8 ? b.R8 : (signed char*)nullptr, b.Mk8, b.sigscale, img == kOpF16 ? 1.0f / b.ascale16 : b.astep, img);
     HIPCHECK(hipGetLastError());
     // Screening error bound  | |<a_n, r>| - s_n | <= cert_abs |r| + cert_rel s_n  (k_b_pick, csmp_batched.hpp).
@@ -482,7 +456,7 @@ static int omp_batch_mfma_chunk(csmp_ctx* ctx, const void* B, int b_dtype, int64
         HIPCHECK(e);
     }
     hipLaunchKernelGGL(k_b_finish, dim3((int)nsig), dim3(256), (size_t)(b.kcap + 2) * 8, ctx->stream, (const double*)b.T,
-                       (const double*)b.z, (const int*)b.sel, (const BState*)b.bs, b.kcap, (int)k, d_idx, d_val, d_nnz);
+                       (const double*)b.z, (const int*)b.sel, (const BState*)b.bs, b.kcap, (int)k, io.d_idx, io.d_val, io.d_nnz);
     HIPCHECK(hipGetLastError());
     // signals whose screen could not be certified (or whose support turned ill-conditioned) are
     // re-solved by the exact single-signal path
@@ -497,21 +471,9 @@ static int omp_batch_mfma_chunk(csmp_ctx* ctx, const void* B, int b_dtype, int64
         b.last_resolved += 1;
         b.last_uncertain += hs[sgn].uncertain ? 1 : 0;
         b.last_illcond += hs[sgn].illcond ? 1 : 0;
-        const char* col = (const char*)dB + (size_t)sgn * (size_t)ldB * es;
-        rc = b_dtype == CSMP_F32 ? init_from_device_t<float>(ctx, (const float*)col)
-                                 : init_from_device_t<double>(ctx, (const double*)col);
-        for (int64_t t = 0; t < k && rc == CSMP_OK; ++t) rc = omp_step(ctx, eps, t > 0, false);
-        if (rc == CSMP_OK) rc = launch_finish(ctx, d_idx + sgn * k, d_val + sgn * k, d_nnz + sgn, nullptr, (int)k);
+        rc = omp_solve_exact(ctx, io, sgn, eps, nullptr);
     }
-    if (out_loc == CSMP_HOST) {
-        if (rc == CSMP_OK) {
-            HIPCHECK(hipMemcpyAsync(idx, d_idx, (size_t)k * nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHECK(hipMemcpyAsync(val, d_val, (size_t)k * nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHECK(hipMemcpyAsync(nnz, d_nnz, (size_t)nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIPCHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return rc;
+    return io.done(rc);
 }
 
 // name of the screening kernel the last csmp_omp_batch_mfma call used (for the bench's roofline line)

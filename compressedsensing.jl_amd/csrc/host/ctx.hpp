@@ -296,6 +296,7 @@ struct DevTmp {
     DevTmp& operator=(const DevTmp&) = delete;
     ~DevTmp() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 1)); }
+    int alloc(csmp_ctx* ctx, size_t bytes) { return dmalloc(ctx, (char**)&p, bytes); }  // (through the fail_alloc hook)
 };
 
 // defined in host/batched.hpp and host/screened.hpp (included later); used by the omp drivers
@@ -318,5 +319,3 @@ static int mp_step_screened(csmp_ctx* ctx);
 static int ompr_sweep_screened(csmp_ctx* ctx, const int* cols_dev, int n);
 static int launch_topS(csmp_ctx* ctx, int S);
 static int omp_step_screened(csmp_ctx* ctx, double eps, int check_eps, bool optimistic);
-static int omp_batch_screened(csmp_ctx* ctx, const void* B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k, double eps,
-                              int64_t* idx, double* val, int64_t* nnz, int out_loc);

@@ -324,60 +324,31 @@ static int run_round(const PlanRound& r, csmp_ctx* ctx, csmp_ctx* tw, bool isfr,
     return isfr ? pipe_ticks<fr_pipe_launch<TA>>(a, pb) : pipe_ticks<tick_pipe_launch<TA>>(a, pb);
 }
 
-// omp (algo = CSMP_ALGO_OMP: p1 = eps) or fr (CSMP_ALGO_FR: p1 = max_eps, p2 = min_delta^2) for every column of B
-static int batch_impl(csmp_ctx* ctx, int algo, const void* B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k,
-                      double eps, double p2, int64_t* idx, double* val, int64_t* nnz, int out_loc) {
-    const bool isfr = algo == CSMP_ALGO_FR;
-    if (!ctx) return CSMP_EINVAL;
-    if (!isfr && !(eps >= 0.0)) return fail(ctx, CSMP_EINVAL, "eps has to be non-negative");
-    if (!B || nsig < 0 || k < 1 || ldB < ctx->M) return fail(ctx, CSMP_EINVAL, "batch: bad arguments");
-    if (b_dtype != CSMP_F32 && b_dtype != CSMP_F64) return fail(ctx, CSMP_EINVAL, "b_dtype must be CSMP_F32 or CSMP_F64");
-    if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
+// omp (isfr false: p1 = eps) or fr (isfr true: p1 = max_eps, p2 = min_delta^2) for every column of B
+static int batch_impl(csmp_ctx* ctx, BatchIO& io, bool isfr, double eps, double p2) {
+    const int64_t nsig = io.nsig, k = io.k;
     HIPCHECK(hipSetDevice(ctx->dev));
     const int kc = (int)std::max<int64_t>(1, std::min<int64_t>(k, ctx->M));
     CHECK(solver_ensure(ctx, kc, (int)k));
     if (isfr) CHECK(fr_ensure(ctx));
     ctx->s.begun = false;
-    const size_t es = b_dtype == CSMP_F32 ? 4 : 8;
-    void* dB = const_cast<void*>(B);
-    DevTmp tB, tIdx, tVal, tNnz;  // freed on every return path
-    if (b_loc == CSMP_HOST) {
-        HIPCHECK(tB.alloc((size_t)ldB * (size_t)nsig * es));
-        dB = tB.p;
-        HIPCHECK(hipMemcpy(dB, B, (size_t)ldB * (size_t)nsig * es, hipMemcpyHostToDevice));
-    }
-    int64_t *d_idx = idx, *d_nnz = nnz;
-    double* d_val = val;
-    if (out_loc == CSMP_HOST) {
-        HIPCHECK(tIdx.alloc((size_t)k * nsig * 8));
-        HIPCHECK(tVal.alloc((size_t)k * nsig * 8));
-        HIPCHECK(tNnz.alloc((size_t)nsig * 8));
-        d_idx = (int64_t*)tIdx.p;
-        d_val = (double*)tVal.p;
-        d_nnz = (int64_t*)tNnz.p;
-    }
+    CHECK(io.stage(false));
     int rc = CSMP_OK;
     activate_slot(ctx, 0);
     if (ctx->s.sigcap < nsig) {
         HIPCHECK(sync_all(ctx));
         dfree(ctx->s.sigflags);
-        HIPCHECK(hipMalloc((void**)&ctx->s.sigflags, (size_t)nsig * sizeof(int)));
+        ctx->s.sigcap = 0;
+        CHECK(dmalloc(ctx, &ctx->s.sigflags, (size_t)nsig));
         ctx->s.sigcap = (int)nsig;
     }
     int* const sigflags = ctx->s.sigflags;  // (a pointer VALUE: ctx->s itself is swapped by activate_slot)
-    auto init = [&](csmp_ctx* c, int64_t sgn) -> int {  // signal sgn into c's active slot
-        const char* col = (const char*)dB + (size_t)sgn * (size_t)ldB * es;
-        return b_dtype == CSMP_F32 ? init_from_device_t<float>(c, (const float*)col) : init_from_device_t<double>(c, (const double*)col);
-    };
-    auto finish = [&](csmp_ctx* c, int64_t sgn) -> int {
-        return launch_finish(c, d_idx + sgn * k, d_val + sgn * k, d_nnz + sgn, nullptr, (int)k, sigflags + sgn);
-    };
-    auto solve_one = [&](int64_t sgn, bool optimistic) -> int {
-        int r2 = init(ctx, sgn);
-        for (int64_t t = 0; t < k && r2 == CSMP_OK; ++t)
-            r2 = isfr ? fr_step(ctx, t == 0, eps, p2, optimistic) : omp_step(ctx, eps, t > 0, optimistic);
-        if (r2 == CSMP_OK) r2 = finish(ctx, sgn);
-        return r2;
+    auto init = [&](csmp_ctx* c, int64_t sgn) -> int { return io.init(c, sgn); };  // signal sgn into c's active slot
+    auto finish = [&](csmp_ctx* c, int64_t sgn) -> int { return io.emit(c, sgn, sigflags + sgn); };
+    auto solve_one = [&](int64_t sgn, bool optimistic) -> int {  // (optimistic false: the exact re-solve, omp_solve_exact's for omp)
+        return batch_solve(ctx, io, sgn, sigflags + sgn, [&](int64_t t) {
+            return isfr ? fr_step(ctx, t == 0, eps, p2, optimistic) : omp_step(ctx, eps, t > 0, optimistic);
+        });
     };
     const BatchSchedule sched = batch_schedule(ctx, isfr, nsig, kc);
     const bool twin = sched == BatchSchedule::Pairs || sched == BatchSchedule::Grouped;
@@ -457,30 +428,17 @@ static int batch_impl(csmp_ctx* ctx, int algo, const void* B, int b_dtype, int64
         for (int64_t sgn = 0; sgn < nsig && rc == CSMP_OK; ++sgn)
             if (hf[sgn] & STOP_REORTH) rc = solve_one(sgn, false);
     }
-    if (out_loc == CSMP_HOST) {
-        if (rc == CSMP_OK) {
-            HIPCHECK(hipMemcpyAsync(idx, d_idx, (size_t)k * nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHECK(hipMemcpyAsync(val, d_val, (size_t)k * nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHECK(hipMemcpyAsync(nnz, d_nnz, (size_t)nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIPCHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return rc;
+    return io.done(rc);
 }
 
 extern "C" int csmp_omp_batch(csmp_ctx* ctx, const void* B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k,
                               double eps, int64_t* idx, double* val, int64_t* nnz, int out_loc) {
     if (!ctx) return CSMP_EINVAL;
-    if ((b_loc != CSMP_HOST && b_loc != CSMP_DEVICE) || (out_loc != CSMP_HOST && out_loc != CSMP_DEVICE))
-        return fail(ctx, CSMP_EINVAL, "b_loc / out_loc must be CSMP_HOST or CSMP_DEVICE");
-    if (screened_on(ctx) && nsig > 0) {
-        if (!(eps >= 0.0)) return fail(ctx, CSMP_EINVAL, "eps has to be non-negative");
-        if (!B || !idx || !val || !nnz || k < 1 || ldB < ctx->M) return fail(ctx, CSMP_EINVAL, "batch: bad arguments");
-        if (b_dtype != CSMP_F32 && b_dtype != CSMP_F64) return fail(ctx, CSMP_EINVAL, "b_dtype must be CSMP_F32 or CSMP_F64");
-        if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
-        return omp_batch_screened(ctx, B, b_dtype, ldB, nsig, b_loc, k, eps, idx, val, nnz, out_loc);
-    }
-    return batch_impl(ctx, CSMP_ALGO_OMP, B, b_dtype, ldB, nsig, b_loc, k, eps, 0.0, idx, val, nnz, out_loc);
+    if (!(eps >= 0.0)) return fail(ctx, CSMP_EINVAL, "eps has to be non-negative");
+    BatchIO io(ctx, B, b_dtype, ldB, nsig, b_loc, k, idx, val, nnz, out_loc);
+    CHECK(io.check());
+    if (screened_on(ctx) && nsig > 0) return omp_batch_screened(ctx, io, eps);
+    return batch_impl(ctx, io, false, eps, 0.0);
 }
 
 // fr(A, B[:,s], max_eps, min_delta, k) for every column of B: the forward-regression sweeps of three signals
@@ -488,10 +446,10 @@ extern "C" int csmp_omp_batch(csmp_ctx* ctx, const void* B, int b_dtype, int64_t
 extern "C" int csmp_fr_batch(csmp_ctx* ctx, const void* B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k,
                              double max_eps, double min_delta, int64_t* idx, double* val, int64_t* nnz, int out_loc) {
     if (!ctx) return CSMP_EINVAL;
-    if ((b_loc != CSMP_HOST && b_loc != CSMP_DEVICE) || (out_loc != CSMP_HOST && out_loc != CSMP_DEVICE))
-        return fail(ctx, CSMP_EINVAL, "b_loc / out_loc must be CSMP_HOST or CSMP_DEVICE");
     if (max_eps != max_eps || min_delta != min_delta) return fail(ctx, CSMP_EINVAL, "fr_batch: max_eps / min_delta is NaN");
-    return batch_impl(ctx, CSMP_ALGO_FR, B, b_dtype, ldB, nsig, b_loc, k, max_eps, min_delta * min_delta, idx, val, nnz, out_loc);
+    BatchIO io(ctx, B, b_dtype, ldB, nsig, b_loc, k, idx, val, nnz, out_loc);
+    CHECK(io.check());
+    return batch_impl(ctx, io, true, max_eps, min_delta * min_delta);
 }
 
 // warm start: support/values -> device lists, r = b - A x

@@ -173,10 +173,9 @@ extern "C" int csmp_gomp(csmp_ctx* ctx, const void* b, int b_dtype, int64_t l, i
 // ---- gomp for many signals: TWO solves in flight, one per stream
 // One signal's step is a chain: the dictionary sweep (HBM-bound, 0.6 ms at config 5), then top-S and the panel append (eight
 // short kernels, ~55 us, a fraction of the chip) -- nothing of the same signal can run beside them.  Another signal's sweep
-// can: signals alternate between this context and a twin (a clone on its own stream), everything is enqueued up front, and
-// the twin's first sweep is held back until this context's first sweep has finished, so that the two chains run OUT of
-// phase: each signal's short stages fall under the other's sweep (in phase they would fall on each other).  Results are
-// those of csmp_gomp signal by signal (the same kernels in the same order on each stream).
+// can: signals alternate between this context and a twin (a clone on its own stream) in the staggered schedule of
+// batch_stagger (host/batch_io.hpp), the two chains out of phase.  Results are those of csmp_gomp signal by signal (the same
+// kernels in the same order on each stream).
 // the first n twins exist and carry this context's options
 static int twins_ensure(csmp_ctx* ctx, int n) {
     for (int t = 0; t < n; ++t) {
@@ -189,33 +188,29 @@ static int twins_ensure(csmp_ctx* ctx, int n) {
     return CSMP_OK;
 }
 
-static int gomp_enqueue(csmp_ctx* c, const void* col_dev, int b_dtype, int64_t l, int64_t k, double eps, bool block, int64_t* d_idx,
-                        double* d_val, int64_t* d_nnz, int* d_flag, hipEvent_t after_first_sweep, bool screened = false) {
-    int rc = b_dtype == CSMP_F32 ? init_from_device_t<float>(c, (const float*)col_dev) : init_from_device_t<double>(c, (const double*)col_dev);
-    if (rc != CSMP_OK) return rc;
+// signal s's gomp solve on c (after_first_sweep: recorded behind its first sweep, when not null)
+static int gomp_enqueue(csmp_ctx* c, const BatchIO& io, int64_t s, int64_t l, double eps, bool block, hipEvent_t after_first_sweep,
+                        bool screened = false) {
+    const int64_t k = io.k;
+    CHECK(io.init(c, s));
     const int main_skip = STOP_EPS | STOP_FULL | STOP_REORTH;
     for (int64_t it = 0; it < k / l; ++it) {  // src/matchingpursuit.jl:130-133
-        rc = screened ? gomp_update_screened(c, l, eps, it > 0, main_skip, block) : gomp_update(c, l, eps, it > 0, main_skip, block);
-        if (rc != CSMP_OK) return rc;
+        CHECK(screened ? gomp_update_screened(c, l, eps, it > 0, main_skip, block) : gomp_update(c, l, eps, it > 0, main_skip, block));
         if (it == 0 && after_first_sweep && hipEventRecord(after_first_sweep, c->stream) != hipSuccess) return CSMP_EHIP;
     }
     const int64_t rem = k % l;
-    if (rem > 0) {  // :134-137: runs even after an eps-break
-        rc = screened ? gomp_update_screened(c, rem, 0.0, 0, STOP_FULL | STOP_REORTH, block) : gomp_update(c, rem, 0.0, 0, STOP_FULL | STOP_REORTH, block);
-        if (rc != CSMP_OK) return rc;
-    }
-    return launch_finish(c, d_idx, d_val, d_nnz, nullptr, (int)k, d_flag);
+    if (rem > 0)  // :134-137: runs even after an eps-break
+        CHECK(screened ? gomp_update_screened(c, rem, 0.0, 0, STOP_FULL | STOP_REORTH, block) : gomp_update(c, rem, 0.0, 0, STOP_FULL | STOP_REORTH, block));
+    return io.emit(c, s, io.flag(s));
 }
 
 extern "C" int csmp_gomp_batch(csmp_ctx* ctx, const void* B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t l, int64_t k,
                                double eps, int64_t* idx, double* val, int64_t* nnz, int out_loc) {
     if (!ctx) return CSMP_EINVAL;
-    if ((b_loc != CSMP_HOST && b_loc != CSMP_DEVICE) || (out_loc != CSMP_HOST && out_loc != CSMP_DEVICE))
-        return fail(ctx, CSMP_EINVAL, "b_loc / out_loc must be CSMP_HOST or CSMP_DEVICE");
     if (!(eps >= 0.0)) return fail(ctx, CSMP_EINVAL, "eps has to be non-negative");  // src/matchingpursuit.jl:127
-    if (!B || nsig < 0 || k < 1 || l < 1 || l > k || ldB < ctx->M) return fail(ctx, CSMP_EINVAL, "gomp_batch: bad arguments (needs 1 <= l <= k)");
-    if (b_dtype != CSMP_F32 && b_dtype != CSMP_F64) return fail(ctx, CSMP_EINVAL, "b_dtype must be CSMP_F32 or CSMP_F64");
-    if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
+    if (l < 1 || l > k) return fail(ctx, CSMP_EINVAL, "gomp_batch: bad arguments (needs 1 <= l <= k)");
+    BatchIO io(ctx, B, b_dtype, ldB, nsig, b_loc, k, idx, val, nnz, out_loc);
+    CHECK(io.check());
     if (nsig == 0) return CSMP_OK;
     HIPCHECK(hipSetDevice(ctx->dev));
     // solves in flight: two (the context and a twin) on the exact sweep -- two 4-GiB sweeps already share the HBM -- and up to
@@ -234,50 +229,15 @@ extern "C" int csmp_gomp_batch(csmp_ctx* ctx, const void* B, int b_dtype, int64_
         }
         cc[q]->s.begun = false;
     }
-    const size_t es = b_dtype == CSMP_F32 ? 4 : 8;
-    void* dB = const_cast<void*>(B);
-    DevTmp tB, tIdx, tVal, tNnz, tFlag;
-    if (b_loc == CSMP_HOST) {
-        HIPCHECK(tB.alloc((size_t)ldB * (size_t)nsig * es));
-        dB = tB.p;
-        HIPCHECK(hipMemcpy(dB, B, (size_t)ldB * (size_t)nsig * es, hipMemcpyHostToDevice));
-    }
-    int64_t *d_idx = idx, *d_nnz = nnz;
-    double* d_val = val;
-    if (out_loc == CSMP_HOST) {
-        HIPCHECK(tIdx.alloc((size_t)k * nsig * 8));
-        HIPCHECK(tVal.alloc((size_t)k * nsig * 8));
-        HIPCHECK(tNnz.alloc((size_t)nsig * 8));
-        d_idx = (int64_t*)tIdx.p;
-        d_val = (double*)tVal.p;
-        d_nnz = (int64_t*)tNnz.p;
-    }
-    HIPCHECK(tFlag.alloc((size_t)nsig * sizeof(int)));
-    int* d_flag = (int*)tFlag.p;
-    HIPCHECK(hipStreamSynchronize(ctx->stream));  // (the caller's buffers and our temporaries are ready before either stream starts)
-    for (int q = 0; q + 1 < T; ++q)
-        if (!cc[q]->ev_twin) HIPCHECK(hipEventCreateWithFlags(&cc[q]->ev_twin, hipEventDisableTiming));
+    CHECK(io.stage(true));
     const bool block = l <= kPanelMax;
     if (screened) {
         if (T == 1) CHECK(screened_ensure(ctx));
         for (int q = 1; q < T; ++q) CHECK(screened_ensure_pair(ctx, cc[q]));
     }
-    for (int64_t sgn = 0; sgn < nsig; ++sgn) {
-        const int q = (int)(sgn % T);
-        csmp_ctx* c = cc[q];
-        const char* col = (const char*)dB + (size_t)sgn * (size_t)ldB * es;
-        if (sgn > 0 && sgn < T) HIPCHECK(hipStreamWaitEvent(c->stream, cc[q - 1]->ev_twin, 0));  // a twin starts one sweep behind: out of phase
-        const int rc = gomp_enqueue(c, col, b_dtype, l, k, eps, block, d_idx + sgn * k, d_val + sgn * k, d_nnz + sgn, d_flag + sgn,
-                                    sgn + 1 < T ? c->ev_twin : nullptr, screened);
-        if (rc != CSMP_OK) {
-            if (c != ctx) ctx->err = c->err;
-            for (int w = 0; w < T; ++w) (void)hipStreamSynchronize(cc[w]->stream);
-            return rc;
-        }
-    }
-    for (int w = 1; w < T; ++w) HIPCHECK(hipStreamSynchronize(cc[w]->stream));
+    CHECK(batch_stagger(cc, T, nsig, [&](csmp_ctx* c, int64_t s, hipEvent_t ev) { return gomp_enqueue(c, io, s, l, eps, block, ev, screened); }));
     std::vector<int> hf((size_t)nsig);
-    HIPCHECK(hipMemcpyAsync(hf.data(), d_flag, (size_t)nsig * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(hipMemcpyAsync(hf.data(), io.d_flag, (size_t)nsig * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     // a panel that failed its DGKS test flagged the solve (nothing committed): that signal again, column by column; a solve
     // with an uncertified pick (screened sweep): again with the exact sweep
@@ -293,23 +253,14 @@ extern "C" int csmp_gomp_batch(csmp_ctx* ctx, const void* B, int b_dtype, int64_
                 if (!blk && !(hf[sgn] & STOP_UNCERTAIN)) break;  // (the column-wise chain flags nothing it cannot handle)
                 blk = false;
             }
-            const char* col = (const char*)dB + (size_t)sgn * (size_t)ldB * es;
-            rc = gomp_enqueue(ctx, col, b_dtype, l, k, eps, blk, d_idx + sgn * k, d_val + sgn * k, d_nnz + sgn, d_flag + sgn, nullptr, false);
+            rc = gomp_enqueue(ctx, io, sgn, l, eps, blk, nullptr);
             if (rc == CSMP_OK) {
-                HIPCHECK(hipMemcpyAsync(&hf[sgn], d_flag + sgn, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHECK(hipMemcpyAsync(&hf[sgn], io.flag(sgn), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
                 HIPCHECK(hipStreamSynchronize(ctx->stream));
             }
         }
     }
-    if (out_loc == CSMP_HOST) {
-        if (rc == CSMP_OK) {
-            HIPCHECK(hipMemcpyAsync(idx, d_idx, (size_t)k * nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHECK(hipMemcpyAsync(val, d_val, (size_t)k * nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHECK(hipMemcpyAsync(nnz, d_nnz, (size_t)nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIPCHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return rc;
+    return io.done(rc);
 }
 
 // state reset + r = b for a fresh factorisation on the same b (SP re-factorises from scratch)
@@ -970,9 +921,9 @@ extern "C" int csmp_sp(csmp_ctx* ctx, const void* b, int b_dtype, int64_t k, dou
 extern "C" int csmp_sp_batch(csmp_ctx* ctx, const void* B, int b_dtype, int64_t ldB, int64_t nsig, int64_t k, double delta, int64_t maxiter,
                              int64_t* idx, double* val, int64_t* nnz, int64_t* iters) {
     if (!ctx) return CSMP_EINVAL;
-    if (!B || nsig < 0 || k < 1 || ldB < ctx->M || !idx || !val || !nnz) return fail(ctx, CSMP_EINVAL, "sp_batch: bad arguments");
-    if (b_dtype != CSMP_F32 && b_dtype != CSMP_F64) return fail(ctx, CSMP_EINVAL, "b_dtype must be CSMP_F32 or CSMP_F64");
-    if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
+    if (!idx || !val || !nnz) return fail(ctx, CSMP_EINVAL, "sp_batch: bad arguments");
+    const BatchIO io(ctx, B, b_dtype, ldB, nsig, CSMP_HOST, k, idx, val, nnz, CSMP_HOST);  // (B stays on the host: a job uploads its column)
+    CHECK(io.check());
     if (2 * k > ctx->M) return fail(ctx, CSMP_ERANGE, "2k > length(b) is invalid for Subspace Pursuit");  // src/twostage.jl:55
     if (k > ctx->N) return fail(ctx, CSMP_ERANGE, "sp: k > number of atoms");
     if (nsig == 0) return CSMP_OK;
@@ -987,12 +938,11 @@ extern "C" int csmp_sp_batch(csmp_ctx* ctx, const void* B, int b_dtype, int64_t 
     }
     if (!ctx->ev_gate) HIPCHECK(hipEventCreateWithFlags(&ctx->ev_gate, hipEventDisableTiming));
     for (int t = 0; t < T; ++t) cc[t]->gate = T > 1 ? &ctx->ev_gate : nullptr;
-    const size_t es = b_dtype == CSMP_F32 ? 4 : 8;
     int64_t sig_of[4] = {-1, -1, -1, -1}, next = 0, finished = 0;
-    int rc = CSMP_OK;
+    int rc = CSMP_OK;  // (every failure from here on lands in rc: the streams are drained below)
     auto start = [&](int t) -> int {
         sig_of[t] = next++;
-        return sp_job_begin(cc[t]->spjob, cc[t], (const char*)B + (size_t)sig_of[t] * (size_t)ldB * es, b_dtype, k, delta, maxiter);
+        return sp_job_begin(cc[t]->spjob, cc[t], io.col(sig_of[t]), b_dtype, k, delta, maxiter);
     };
     for (int t = 0; t < T && rc == CSMP_OK; ++t) rc = start(t);
     int spins = 0;
@@ -1002,10 +952,10 @@ extern "C" int csmp_sp_batch(csmp_ctx* ctx, const void* B, int b_dtype, int64_t 
             if (sig_of[t] < 0) continue;
             SpJob& j = cc[t]->spjob;
             if (j.phase != SpJob::DONE) {
-                const hipError_t q = hipEventQuery(j.ev);
+                hipError_t q = hipEventQuery(j.ev);
                 if (q == hipErrorNotReady) continue;
+                if (q == hipSuccess) q = hipSetDevice(ctx->dev);
                 if (q != hipSuccess) { rc = fail(ctx, CSMP_EHIP, hipGetErrorString(q)); break; }
-                HIPCHECK(hipSetDevice(ctx->dev));
                 rc = sp_job_advance(j);
                 moved = true;
                 if (rc != CSMP_OK || j.phase != SpJob::DONE) continue;

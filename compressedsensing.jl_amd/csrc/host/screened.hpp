@@ -295,26 +295,13 @@ static int screened_ensure_pair(csmp_ctx* ctx, csmp_ctx* twin) {
     return rc;
 }
 
-// omp for many signals with the screened sweep: TWO solves in flight, the context's and a twin's, out of phase (the pattern of
-// csmp_gomp_batch): one signal's pick and append stages run under the other's sweep.  A signal whose solve was flagged --
-// an uncertified pick, or a column that failed the DGKS test of the optimistic append chain -- is solved again by the exact
-// path after the one synchronisation.
-static int omp_screened_enqueue(csmp_ctx* c, const void* col_dev, int b_dtype, int64_t k, double eps, int64_t* d_idx, double* d_val,
-                                int64_t* d_nnz, int* d_flag, hipEvent_t after_first_sweep) {
-    int rc = b_dtype == CSMP_F32 ? init_from_device_t<float>(c, (const float*)col_dev) : init_from_device_t<double>(c, (const double*)col_dev);
-    for (int64_t t = 0; t < k && rc == CSMP_OK; ++t) {
-        rc = omp_step_screened(c, eps, t > 0, true);
-        if (t == 0 && rc == CSMP_OK && after_first_sweep && hipEventRecord(after_first_sweep, c->stream) != hipSuccess) return CSMP_EHIP;
-    }
-    if (rc != CSMP_OK) return rc;
-    return launch_finish(c, d_idx, d_val, d_nnz, nullptr, (int)k, d_flag);
-}
-
-static int omp_batch_screened(csmp_ctx* ctx, const void* B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k, double eps,
-                              int64_t* idx, double* val, int64_t* nnz, int out_loc) {
-    if (nsig == 0) return CSMP_OK;
+// omp for many signals with the screened sweep: up to three solves in flight, the context's and its twins', in the staggered
+// schedule of batch_stagger (host/batch_io.hpp): one signal's pick and append stages run under another's sweep.  A signal whose
+// solve was flagged -- an uncertified pick, or a column that failed the DGKS test of the optimistic append chain -- is solved
+// again by the exact path after the one synchronisation.
+static int omp_batch_screened(csmp_ctx* ctx, BatchIO& io, double eps) {
+    const int64_t nsig = io.nsig, k = io.k;
     HIPCHECK(hipSetDevice(ctx->dev));
-    // solves in flight: the context's and its twins', each one sweep behind the previous one
     int T = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ctx->opt_in_flight, 3), nsig));  // (CSMP_OPT_SOLVES_IN_FLIGHT)
     if (T > 1) CHECK(twins_ensure(ctx, T - 1));
     csmp_ctx* cc[3] = {ctx, T > 1 ? ctx->twins[0] : nullptr, T > 2 ? ctx->twins[1] : nullptr};
@@ -329,70 +316,30 @@ static int omp_batch_screened(csmp_ctx* ctx, const void* B, int b_dtype, int64_t
         }
         cc[q]->s.begun = false;
     }
-    const size_t es = b_dtype == CSMP_F32 ? 4 : 8;
-    void* dB = const_cast<void*>(B);
-    DevTmp tB, tIdx, tVal, tNnz, tFlag;
-    if (b_loc == CSMP_HOST) {
-        HIPCHECK(tB.alloc((size_t)ldB * (size_t)nsig * es));
-        dB = tB.p;
-        HIPCHECK(hipMemcpy(dB, B, (size_t)ldB * (size_t)nsig * es, hipMemcpyHostToDevice));
-    }
-    int64_t *d_idx = idx, *d_nnz = nnz;
-    double* d_val = val;
-    if (out_loc == CSMP_HOST) {
-        HIPCHECK(tIdx.alloc((size_t)k * nsig * 8));
-        HIPCHECK(tVal.alloc((size_t)k * nsig * 8));
-        HIPCHECK(tNnz.alloc((size_t)nsig * 8));
-        d_idx = (int64_t*)tIdx.p;
-        d_val = (double*)tVal.p;
-        d_nnz = (int64_t*)tNnz.p;
-    }
-    HIPCHECK(tFlag.alloc((size_t)nsig * sizeof(int)));
-    int* d_flag = (int*)tFlag.p;
-    HIPCHECK(hipStreamSynchronize(ctx->stream));
-    for (int q = 0; q + 1 < T; ++q)
-        if (!cc[q]->ev_twin) HIPCHECK(hipEventCreateWithFlags(&cc[q]->ev_twin, hipEventDisableTiming));
-    for (int64_t sgn = 0; sgn < nsig; ++sgn) {
-        const int q = (int)(sgn % T);
-        csmp_ctx* c = cc[q];
-        const char* col = (const char*)dB + (size_t)sgn * (size_t)ldB * es;
-        if (sgn > 0 && sgn < T) HIPCHECK(hipStreamWaitEvent(c->stream, cc[q - 1]->ev_twin, 0));  // a twin starts one sweep behind: out of phase
-        const int rc = omp_screened_enqueue(c, col, b_dtype, k, eps, d_idx + sgn * k, d_val + sgn * k, d_nnz + sgn, d_flag + sgn,
-                                            sgn + 1 < T ? c->ev_twin : nullptr);
-        if (rc != CSMP_OK) {
-            if (c != ctx) ctx->err = c->err;
-            for (int w = 0; w < T; ++w) (void)hipStreamSynchronize(cc[w]->stream);
+    CHECK(io.stage(true));
+    CHECK(batch_stagger(cc, T, nsig, [&](csmp_ctx* c, int64_t s, hipEvent_t after_first_sweep) {
+        return batch_solve(c, io, s, io.flag(s), [&](int64_t t) {
+            const int rc = omp_step_screened(c, eps, t > 0, true);
+            if (t == 0 && rc == CSMP_OK && after_first_sweep && hipEventRecord(after_first_sweep, c->stream) != hipSuccess) return CSMP_EHIP;
             return rc;
-        }
-    }
-    for (int w = 1; w < T; ++w) HIPCHECK(hipStreamSynchronize(cc[w]->stream));
+        });
+    }));
     std::vector<int> hf((size_t)nsig);
-    HIPCHECK(hipMemcpyAsync(hf.data(), d_flag, (size_t)nsig * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(hipMemcpyAsync(hf.data(), io.d_flag, (size_t)nsig * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     int rc = CSMP_OK;
     for (int64_t sgn = 0; sgn < nsig && rc == CSMP_OK; ++sgn) {
         ctx->scr_solves += 1;
         if (hf[sgn] & (STOP_REORTH | STOP_UNCERTAIN)) {  // again, by the exact path with the full append chain
             ctx->scr_fallbacks += (hf[sgn] & STOP_UNCERTAIN) ? 1 : 0;
-            const char* col = (const char*)dB + (size_t)sgn * (size_t)ldB * es;
-            rc = b_dtype == CSMP_F32 ? init_from_device_t<float>(ctx, (const float*)col) : init_from_device_t<double>(ctx, (const double*)col);
-            for (int64_t t = 0; t < k && rc == CSMP_OK; ++t) rc = omp_step(ctx, eps, t > 0, false);
-            if (rc == CSMP_OK) rc = launch_finish(ctx, d_idx + sgn * k, d_val + sgn * k, d_nnz + sgn, nullptr, (int)k, d_flag + sgn);
+            rc = omp_solve_exact(ctx, io, sgn, eps, io.flag(sgn));
             if (rc == CSMP_OK) {
-                HIPCHECK(hipMemcpyAsync(&hf[sgn], d_flag + sgn, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHECK(hipMemcpyAsync(&hf[sgn], io.flag(sgn), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
                 HIPCHECK(hipStreamSynchronize(ctx->stream));
             }
         }
     }
-    if (out_loc == CSMP_HOST) {
-        if (rc == CSMP_OK) {
-            HIPCHECK(hipMemcpyAsync(idx, d_idx, (size_t)k * nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHECK(hipMemcpyAsync(val, d_val, (size_t)k * nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHECK(hipMemcpyAsync(nnz, d_nnz, (size_t)nsig * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIPCHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return rc;
+    return io.done(rc);
 }
 
 // screened solves made by this context and how many of them were repeated with the exact sweep (failed certificate)

@@ -161,13 +161,23 @@ def test_every_allocation_may_fail(cs, dtype):
     gc.collect()
     base = L.live_resources()
     # (pipelines 2: the twin context's allocations are among those that fail in turn; omp_batch once more under the grouped scheduler,
-    # groups of two: the slots beyond the first three of both contexts fail in turn too)
-    cases = [(name, f, {"pipelines": 2}, 200) for name, f in sorted(fam.items())]
-    cases.append(("omp_batch", fam["omp_batch"], {"pipelines": 3, "group_max": 2}, 600))
-    for name, f, tunes, most in cases:
-        clean = cs.Dictionary(A)
+    # groups of two: the slots beyond the first three of both contexts fail in turn too; the staggered schedule of the screened omp /
+    # gomp batches with three solves in flight and sp_batch with four: the call's staged B, outputs and flags fail in turn)
+    cases = [(name, f, {"pipelines": 2}, {}, 200) for name, f in sorted(fam.items())]
+    cases.append(("omp_batch", fam["omp_batch"], {"pipelines": 3, "group_max": 2}, {}, 600))
+    for name in ("omp_batch", "gomp_batch"):
+        cases.append((name, fam[name], {}, {"screened_sweep": 1, "solves_in_flight": 3}, 400))
+    cases.append(("sp_batch", fam["sp_batch"], {}, {"solves_in_flight": 4}, 400))
+
+    def setup(ctx, tunes, options):
         for key, v in tunes.items():
-            clean.ctx.tune(key, v)
+            ctx.tune(key, v)
+        for key, v in options.items():
+            ctx.set_option(key, v)
+
+    for name, f, tunes, options, most in cases:
+        clean = cs.Dictionary(A)
+        setup(clean.ctx, tunes, options)
         assert clean.ctx.sweep_config()["group_max"] == tunes.get("group_max", clean.ctx.sweep_config()["group_max"])
         want = f(clean.ctx)
         clean.close()
@@ -175,20 +185,19 @@ def test_every_allocation_may_fail(cs, dtype):
         while seen_ok < 2 and n < most:  # (two successes in a row: n is past every allocation of the call)
             n += 1
             d = cs.Dictionary(A)
-            for key, v in tunes.items():
-                d.ctx.tune(key, v)
+            setup(d.ctx, tunes, options)
             d.ctx.tune("fail_alloc", n)
             try:
                 got = f(d.ctx)
-                assert _same(got, want), (name, tunes, n, "the call went through with a result of its own")
+                assert _same(got, want), (name, tunes, options, n, "the call went through with a result of its own")
                 seen_ok += 1
             except cs.CsmpError as e:
                 seen_ok = 0
-                assert e.code in (L.EHIP, L.ENOMEM), (name, tunes, n, e.code, str(e))
+                assert e.code in (L.EHIP, L.ENOMEM), (name, tunes, options, n, e.code, str(e))
             d.ctx.tune("fail_alloc", 0)
             got = f(d.ctx)
-            assert _same(got, want), (name, tunes, n, "after the failed call")
+            assert _same(got, want), (name, tunes, options, n, "after the failed call")
             d.close()
-        assert n < most, (name, tunes)
+        assert n < most, (name, tunes, options)
     gc.collect()
     assert L.live_resources() == base
