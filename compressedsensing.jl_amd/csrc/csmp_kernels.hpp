@@ -2094,11 +2094,26 @@ __global__ __launch_bounds__(DYN ? kSweepDynThreads : kSweepThreads) void k_tick
 // Shared sweep: ONE pass over the dictionary computes c = A' r for up to kGroupMax residuals (the signals of one group of the
 // grouped batch scheduler, host/omp.hpp).  The ring, the unit loads, the clamped ragged rows and the early first loads are
 // sweep_body_gen's; every A value is promoted once and multiplied into R accumulators, one per residual, each against its own LDS
-// image (r_slot layout).  Per residual the arithmetic is sweep_body_gen's alone: the same fma order per lane, the same wave_xsum,
-// ||r||^2 in the same per-thread order, its own staged c stores and its own (max |c|, first index) partials -- the same bits.
-// A member that is already stopped (st->done & skipmask) or stops on eps in this pass is masked: it writes no c and no partials.
-// The pass returns early only when every member is stopped.  dynamic LDS: R images of KP doubles + the scratch (sweep_multi_lds_bytes).
+// image (r_slot layout).  Per residual the arithmetic is sweep_body_gen's alone: the same fma order per lane over the same KP rows,
+// the same wave_xsum, ||r||^2 in the same per-thread order, its own staged c stores and its own (max |c|, first index) partials --
+// the same bits.  A member that is already stopped (st->done & skipmask) or stops on eps in this pass is masked: it writes no c and
+// no partials.  The pass returns early only when every member is stopped.
+//   waves   kMultiThreads = 512: TWO waves per SIMD share the R images (the LDS request keeps one workgroup per CU).  With one
+//           wave per SIMD (round 7's body) every pair of fmas waited for an LDS round trip, and those waits sat on the ring: a
+//           wave's next loads go out only after a unit is consumed.  With two, one wave's waits are covered by the other's issue.
+//   pairs   a wave takes the columns 2q and 2q + 1 at once (pair q = wave + 8 * workgroup, strided by the grid's waves): every
+//           image value read from the LDS feeds both columns' fmas, half the ds_read_b128 per byte of A.  Each column keeps its
+//           own accumulator chain.  A last pair of an odd N clamps its second column to N - 1 and discards it.
+//   reads   the image values of the next row group are read one step ahead of the fmas (all 2R or R slots in flight together).
+//   ring    U = 4 loads per column and unit, NB = 2 units: 16 KiB per wave, 128 KiB per CU; in the steady loop each load's
+//           registers are refilled with the unit NB ahead as soon as the load is converted.
+//   f64     Float64 dictionaries keep round 7's four-wave body (sweep_body_multi_w4 below).
+//   norm    member i's image and ||r||^2 are staged by the half of the workgroup i & 1 names: its 256 threads run
+//           sweep_body_gen's loop over t = tid & 255 -- every thread's partial sum, and the sums over the four waves of the half,
+//           are the single body's.
+// dynamic LDS: R images of KP doubles + the scratch (sweep_multi_lds_bytes).
 constexpr int kGroupMax = 4;
+constexpr int kMultiThreads = 512;  // k_sweep_multi: 8 waves
 template <typename TA>
 struct MultiSweep {
     const TA* A; int64_t ld; int Mv; int64_t N;
@@ -2106,9 +2121,279 @@ struct MultiSweep {
     int n;  // members (1 .. R; the launch's R is n)
     const double* r[kGroupMax]; double* cvec[kGroupMax]; double* pval[kGroupMax]; int* pidx[kGroupMax]; DevState* st[kGroupMax];
 };
-inline size_t sweep_multi_lds_bytes(int KP, int R) { return ((size_t)R * KP + 16 + 32 * (size_t)R) * sizeof(double); }
+// images + ||r||^2 partials [4 waves of a half x R <= 16] + arg-max partials [R][4 per wave x 8 waves] (doubles, then ints)
+inline size_t sweep_multi_lds_bytes(int KP, int R) {
+    const size_t nred = (size_t)R * 4 * (kMultiThreads / kWave);
+    return ((size_t)R * KP + 16 + nred) * sizeof(double) + nred * sizeof(int);
+}
 template <typename TA, int U, int NB, int R>
 __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const int bid, double* lds) {
+    using VT = typename Vec<TA>::type;
+    constexpr int VEC = Vec<TA>::n;
+    constexpr int ROWS = kWave * VEC;
+    constexpr int UR = U * ROWS;
+    constexpr int NW = kMultiThreads / kWave;
+    static_assert((NB - 1) * 2 * U < 64, "the ring must fit the 6-bit vmcnt");
+    static_assert(R >= 1 && R <= kGroupMax, "group size");
+    unsigned live = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+        if (!(p.st[i]->done & p.skipmask)) live |= 1u << i;
+    if (!live) return;
+    const TA* __restrict__ A = p.A;
+    const int64_t ld = p.ld, N = p.N;
+    const int Mv = p.Mv, KP = p.KP, nblk = p.nblk;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nvec = Mv / VEC;
+    double* n2s = lds + (size_t)R * KP;  // [4 waves of a half x R]
+    double* redv = n2s + 16;             // [R][4 NW]
+    int* redi = reinterpret_cast<int*>(redv + 4 * NW * R);
+
+    // pair q = columns 2q and 2q + 1 (the second clamped to N - 1 and discarded where it is N)
+    const int64_t NP = (N + 1) / 2;
+    const int64_t q0 = (int64_t)bid * NW + wave, stride = (int64_t)nblk * NW;
+    const int64_t npair = q0 < NP ? (NP - 1 - q0) / stride + 1 : 0;
+    double bestv[R];
+    int besti[R];
+    const int nunit = KP / UR;  // every row of the image, as sweep_body_gen runs them (its KP is a whole number of 4-load units)
+    const int Mst = KP;
+    VT buf[NB][2][U];
+    double cst[R], acc[2][R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        bestv[i] = -1.0;
+        besti[i] = 0x7fffffff;
+        cst[i] = 0.0;
+        acc[0][i] = acc[1][i] = 0.0;
+    }
+    int64_t ccst = -1;
+    int cslot = 0;
+    int64_t iq = q0, cq = q0;
+    int ib = 0, cb = 0;
+    const int64_t T = npair * nunit;
+    int64_t ileft = T, cleft = T;
+    auto issue = [&](VT(&b)[2][U]) {
+        const int64_t c0 = 2 * iq, c1 = c0 + 1 < N ? c0 + 1 : N - 1;
+        const VT* p0 = reinterpret_cast<const VT*>(A + c0 * ld);
+        const VT* p1 = reinterpret_cast<const VT*>(A + c1 * ld);
+        const int vb = ib * (U * kWave) + lane;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int v = vb + u * kWave;
+            b[0][u] = __builtin_nontemporal_load(p0 + (v < nvec ? v : nvec - 1));
+            b[1][u] = __builtin_nontemporal_load(p1 + (v < nvec ? v : nvec - 1));
+        }
+        if (++ib == nunit) {
+            ib = 0;
+            iq += stride;
+        }
+        --ileft;
+    };
+#pragma unroll
+    for (int d = 0; d < NB; ++d) {
+        if (ileft <= 0) {
+            iq = (npair > 0 ? q0 + (npair - 1) * stride : NP - 1);
+            ib = 0;
+        }
+        issue(buf[d]);
+    }
+    {
+        // the images and every member's ||r||^2, each in sweep_body_gen's per-thread order (t: the thread's index in its half)
+        constexpr int RP = 16;
+        const int half = wave >> 2, t = tid & (kSweepThreads - 1);
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            if ((i & 1) != half) continue;
+            const double* __restrict__ r = p.r[i];
+            double* img = lds + (size_t)i * KP;
+            double n2 = 0.0;
+            for (int m0 = t; m0 < Mst; m0 += RP * kSweepThreads) {
+                double rv[RP];
+#pragma unroll
+                for (int q = 0; q < RP; ++q) {
+                    const int m = m0 + q * kSweepThreads;
+                    rv[q] = m < Mv ? r[m] : 0.0;
+                }
+#pragma unroll
+                for (int q = 0; q < RP; ++q) {
+                    const int m = m0 + q * kSweepThreads;
+                    if (m < Mst) img[r_slot<VEC>(m)] = rv[q];
+                    n2 = fma(rv[q], rv[q], n2);
+                }
+            }
+            for (int s = 32; s >= 1; s >>= 1) n2 += __shfl_xor(n2, s, kWave);
+            if (lane == 0) n2s[(wave & 3) * R + i] = n2;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            if (!(live & (1u << i))) continue;
+            const double n2 = (n2s[0 * R + i] + n2s[1 * R + i]) + (n2s[2 * R + i] + n2s[3 * R + i]);
+            if (bid == 0 && tid == 0) p.st[i]->rnorm2 = n2;
+            if (p.check_eps && !(sqrt(n2) >= p.eps)) {  // norm(residual!) >= eps || break  (:79,:132)
+                if (bid == 0 && tid == 0) p.st[i]->done |= STOP_EPS;
+                live &= ~(1u << i);
+            }
+        }
+        if (!live) return;
+    }
+    // the image values of the next row group (R x SL slots) are read one step AHEAD of the fmas that use them, across unit and
+    // column boundaries (the images do not change during the pass): the reads of a step are in flight together, behind the
+    // arithmetic of the step before, instead of each pair of fmas waiting for a round trip of its own
+    constexpr int SL = VEC / 2;  // 16-B slots of an image per lane and load of A
+    f64x2 nx[R][SL];
+    auto read_img = [&](int t) {
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const f64x2* rs = reinterpret_cast<const f64x2*>(lds + (size_t)i * KP);
+#pragma unroll
+            for (int h = 0; h < SL; ++h) nx[i][h] = rs[(t * SL + h) * kWave + lane];
+        }
+    };
+    read_img(0);
+    // step: consume the unit in b; with REFILL each load's registers are refilled with the unit NB ahead as soon as the load is
+    // converted (the steady loop: every load unconditional), else the caller issues the next unit after the step
+    auto step = [&](VT(&b)[2][U], auto refill) {
+        constexpr bool REFILL = decltype(refill)::value;
+        const VT* p0 = nullptr;
+        const VT* p1 = nullptr;
+        int vb = 0;
+        if constexpr (REFILL) {
+            const int64_t c0 = 2 * iq, c1 = c0 + 1 < N ? c0 + 1 : N - 1;
+            p0 = reinterpret_cast<const VT*>(A + c0 * ld);
+            p1 = reinterpret_cast<const VT*>(A + c1 * ld);
+            vb = ib * (U * kWave) + lane;
+            if (++ib == nunit) {
+                ib = 0;
+                iq += stride;
+            }
+            --ileft;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            f64x2 cur[R][SL];
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+#pragma unroll
+                for (int h = 0; h < SL; ++h) cur[i][h] = nx[i][h];
+            read_img(u + 1 < U ? cb * U + u + 1 : (cb + 1 == nunit ? 0 : (cb + 1) * U));
+            double a[2][VEC];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                a[j][0] = (double)b[j][u].x;
+                a[j][1] = (double)b[j][u].y;
+                if constexpr (VEC == 4) {
+                    a[j][2] = (double)b[j][u].z;
+                    a[j][3] = (double)b[j][u].w;
+                }
+            }
+            if constexpr (REFILL) {
+                const int v = vb + u * kWave;
+                b[0][u] = __builtin_nontemporal_load(p0 + (v < nvec ? v : nvec - 1));
+                b[1][u] = __builtin_nontemporal_load(p1 + (v < nvec ? v : nvec - 1));
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {  // both columns of the pair against the same image values
+#pragma unroll
+                for (int i = 0; i < R; ++i) {
+                    acc[j][i] = fma(a[j][0], cur[i][0].x, acc[j][i]);
+                    acc[j][i] = fma(a[j][1], cur[i][0].y, acc[j][i]);
+                    if constexpr (VEC == 4) {
+                        acc[j][i] = fma(a[j][2], cur[i][1].x, acc[j][i]);
+                        acc[j][i] = fma(a[j][3], cur[i][1].y, acc[j][i]);
+                    }
+                }
+            }
+        }
+        if (++cb == nunit) {  // the pair's last unit: column 2q, then 2q + 1 where it exists
+            const int64_t c0 = 2 * cq;
+            const bool two = c0 + 1 < N;
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const double c = wave_xsum(acc[j][i]);
+                    acc[j][i] = 0.0;
+                    if (j == 1 && !two) continue;
+                    if (lane == cslot + j) cst[i] = c;
+                    const double av = fabs(c);
+                    if (av > bestv[i]) {  // columns arrive in increasing order: '>' keeps the first maximum
+                        bestv[i] = av;
+                        besti[i] = (int)(c0 + j);
+                    }
+                }
+            }
+            if (lane == cslot) ccst = c0;
+            if (lane == cslot + 1) ccst = two ? c0 + 1 : -1;
+            cslot += 2;
+            if (cslot == kWave) {
+                if (ccst >= 0) {
+#pragma unroll
+                    for (int i = 0; i < R; ++i)
+                        if (live & (1u << i)) p.cvec[i][ccst] = cst[i];
+                }
+                ccst = -1;
+                cslot = 0;
+            }
+            cb = 0;
+            cq += stride;
+        }
+        --cleft;
+    };
+    if (T >= 2 * NB) {
+        const int64_t groups = T / NB - 1;
+        for (int64_t g = 0; g < groups; ++g) {
+#pragma unroll
+            for (int d = 0; d < NB; ++d) step(buf[d], std::true_type{});
+        }
+    }
+    while (cleft > 0) {
+#pragma unroll
+        for (int d = 0; d < NB; ++d) {
+            if (cleft == 0) break;
+            step(buf[d], std::false_type{});
+            if (ileft > 0) issue(buf[d]);
+        }
+    }
+    if (ccst >= 0) {
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (live & (1u << i)) p.cvec[i][ccst] = cst[i];
+    }
+    if ((lane & 15) == 0) {
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            redv[i * 4 * NW + wave * 4 + (lane >> 4)] = bestv[i];
+            redi[i * 4 * NW + wave * 4 + (lane >> 4)] = besti[i];
+        }
+    }
+    __syncthreads();
+    if (tid < R && (live & (1u << tid))) {  // thread i reduces member i's partials with better(): the first maximum of the workgroup
+        const double* rv = redv + tid * 4 * NW;
+        const int* ri = redi + tid * 4 * NW;
+        double bv = rv[0];
+        int bi = ri[0];
+        for (int q = 1; q < 4 * NW; ++q)
+            if (better(rv[q], ri[q], bv, bi)) {
+                bv = rv[q];
+                bi = ri[q];
+            }
+        p.pval[tid][bid] = bv;
+        p.pidx[tid][bid] = bi;
+    }
+}
+// U loads per column and unit, NB = 2 units in the ring
+template <typename TA, int U, int R>
+__global__ __launch_bounds__(kMultiThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_multi(const MultiSweep<TA> p) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    sweep_body_multi<TA, U, 2, R>(p, (int)blockIdx.x, lds);
+}
+
+// The shared sweep of round 7 (four waves, one column each, ring U / 32 / U as the single body's), kept for Float64 dictionaries:
+// the 512-thread pair body above measured 6 % slower there (4096 x 32768 f64, 6 and 18 signals, 4- and 8-load units alike).
+template <typename TA, int U, int NB, int R>
+__device__ __forceinline__ void sweep_body_multi_w4(const MultiSweep<TA>& p, const int bid, double* lds) {
     using VT = typename Vec<TA>::type;
     constexpr int VEC = Vec<TA>::n;
     constexpr int ROWS = kWave * VEC;
@@ -2127,7 +2412,7 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nvec = Mv / VEC;
-    double* n2s = lds + (size_t)R * KP;  // [4 waves x R]
+    double* n2s = lds + (size_t)R * KP;  // [4 waves x R]  (the scratch of sweep_multi_lds_bytes holds this layout)
     double* redv = n2s + 16;             // [R][4 NW]
     int* redi = reinterpret_cast<int*>(redv + 16 * R);
 
@@ -2312,9 +2597,9 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
     }
 }
 template <typename TA, int U, int R>
-__global__ __launch_bounds__(kSweepThreads) void k_sweep_multi(const MultiSweep<TA> p) {
+__global__ __launch_bounds__(kSweepThreads) void k_sweep_multi_w4(const MultiSweep<TA> p) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    sweep_body_multi<TA, U, 32 / U, R>(p, (int)blockIdx.x, lds);
+    sweep_body_multi_w4<TA, U, 32 / U, R>(p, (int)blockIdx.x, lds);
 }
 
 // The append stages of two groups in ONE launch (the grouped scheduler's companion of k_tick's stages [0, 2G)): G workgroups per

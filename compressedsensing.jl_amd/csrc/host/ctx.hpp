@@ -152,6 +152,7 @@ struct SpJob {
 
 
 constexpr int kPairTickGrid = 192;  // sweep workgroups of each of two pipelines side by side (measured: 176 -> 6.41e3, 192 -> 6.46e3, 224 -> 6.45e3, 256 -> 6.41e3 atoms/s)
+constexpr int kGroupTickGrid = 208;  // shared-sweep workgroups (k_sweep_multi, 8 waves) of each of two pipelines (measured at 4096 x 65536 f32, 18 signals: 160 -> 21.38e3, 171 -> 20.67e3, 192 -> 21.04e3, 205 -> 21.44e3, 208 -> 21.57e3, 216 -> 21.48e3 atoms/s)
 constexpr int kSlots = 3 * kGroupMax;  // solver slots of a context: three groups of the grouped batch scheduler (host/omp.hpp)
 struct csmp_ctx {
     SpJob spjob;  // the Subspace Pursuit solve this context is carrying (csmp_sp, csmp_sp_batch, the SP functor)

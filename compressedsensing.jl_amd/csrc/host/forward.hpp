@@ -299,7 +299,7 @@ static void pipe_begin(Pipe& p, csmp_ctx* c, const PlanGroup g[3], RoundForm for
     }
     // Measured at 4096 x 65536 f32: 8-chunk load blocks on ONE workgroup per CU (the append stages of the other two signals share
     // those CUs) 160.4 us per tick; 16-chunk blocks on 176 workgroups (11/12 of the stand-alone sweep's optimum of 192) 162.6 us.
-    p.nblk = pipe_nblk(c, form == RoundForm::One ? c->tick_grid : kPairTickGrid);  // (tick_grid: configure_sweep)
+    p.nblk = pipe_nblk(c, form == RoundForm::One ? c->tick_grid : form == RoundForm::Grouped && c->dtype == CSMP_F32 ? kGroupTickGrid : kPairTickGrid);  // (tick_grid: configure_sweep)
     if (form == RoundForm::Grouped) {
         p.lds = qr_lds;
         p.lds_sweep = excl;

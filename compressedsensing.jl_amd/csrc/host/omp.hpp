@@ -148,12 +148,16 @@ static int tick_pipe_launch(Pipe& tp, int64_t n) {
 // signal gets the same bits.
 template <typename TA, int U, int R>
 static hipError_t multi_launch_t(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t lds) {
-    auto kern = k_sweep_multi<TA, U, R>;
+    constexpr bool w4 = Vec<TA>::n == 2;  // Float64: round 7's four-wave body (csmp_kernels.hpp)
+    auto kern = [] {
+        if constexpr (w4) return k_sweep_multi_w4<TA, U, R>;
+        else return k_sweep_multi<TA, 4, R>;
+    }();
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(kSweepThreads), lds, ctx->stream, p);
+    hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(w4 ? kSweepThreads : kMultiThreads), lds, ctx->stream, p);
     return hipGetLastError();
 }
 template <typename TA, int U>
@@ -165,13 +169,17 @@ static hipError_t multi_launch_u(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t 
         default: return multi_launch_t<TA, U, 4>(ctx, p, lds);
     }
 }
+// Float32: the 512-thread pair body, whose unit is its own (4 loads per column); Float64: the four-wave body on ctx->sweep_U
 template <typename TA>
 static hipError_t multi_launch(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t lds) {
-    switch (ctx->sweep_U) {
-        case 16: return multi_launch_u<TA, 16>(ctx, p, lds);
-        case 8: return multi_launch_u<TA, 8>(ctx, p, lds);
-        default: return multi_launch_u<TA, 4>(ctx, p, lds);
+    if constexpr (Vec<TA>::n == 2) {
+        switch (ctx->sweep_U) {
+            case 16: return multi_launch_u<TA, 16>(ctx, p, lds);
+            case 8: return multi_launch_u<TA, 8>(ctx, p, lds);
+            default: return multi_launch_u<TA, 4>(ctx, p, lds);
+        }
     }
+    return multi_launch_u<TA, 4>(ctx, p, lds);
 }
 template <typename TA>
 static int group_pipe_launch(Pipe& gp, int64_t n) {
