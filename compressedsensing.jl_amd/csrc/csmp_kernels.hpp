@@ -2112,22 +2112,26 @@ __global__ __launch_bounds__(DYN ? kSweepDynThreads : kSweepThreads) void k_tick
 //           sweep_body_gen's loop over t = tid & 255 -- every thread's partial sum, and the sums over the four waves of the half,
 //           are the single body's.
 // dynamic LDS: R images of KP doubles + the scratch (sweep_multi_lds_bytes).
-constexpr int kGroupMax = 4;
+constexpr int kGroupMax = 4;             // images per workgroup
+constexpr int kWideMax = 2 * kGroupMax;  // members of a wide pass (k_sweep_wide below): two halves of up to kGroupMax
 constexpr int kMultiThreads = 512;  // k_sweep_multi: 8 waves
 template <typename TA>
 struct MultiSweep {
     const TA* A; int64_t ld; int Mv; int64_t N;
     double eps; int check_eps, skipmask, nblk, KP;
-    int n;  // members (1 .. R; the launch's R is n)
-    const double* r[kGroupMax]; double* cvec[kGroupMax]; double* pval[kGroupMax]; int* pidx[kGroupMax]; DevState* st[kGroupMax];
+    int n;   // members (1 .. R; the launch's R is n); the wide pass: members of half 0, entries [0, n)
+    int n1;  // the wide pass: members of half 1 (n - 1 or n), entries [kGroupMax, kGroupMax + n1); 0: the narrow pass
+    const double* r[kWideMax]; double* cvec[kWideMax]; double* pval[kWideMax]; int* pidx[kWideMax]; DevState* st[kWideMax];
 };
 // images + ||r||^2 partials [4 waves of a half x R <= 16] + arg-max partials [R][4 per wave x 8 waves] (doubles, then ints)
 inline size_t sweep_multi_lds_bytes(int KP, int R) {
     const size_t nred = (size_t)R * 4 * (kMultiThreads / kWave);
     return ((size_t)R * KP + 16 + nred) * sizeof(double) + nred * sizeof(int);
 }
-template <typename TA, int U, int NB, int R>
-__device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const int bid, double* lds) {
+// bid of nblk: the workgroup's column stream; mo, nmem: its members are the entries [mo, mo + nmem) (an entry [mo + nmem, mo + R) is
+// masked like a stopped member).  NT: the ring's loads are nontemporal.
+template <typename TA, int U, int NB, int R, bool NT = true>
+__device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const int bid, const int nblk, const int mo, const int nmem, double* lds) {
     using VT = typename Vec<TA>::type;
     constexpr int VEC = Vec<TA>::n;
     constexpr int ROWS = kWave * VEC;
@@ -2138,11 +2142,11 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
     unsigned live = 0;
 #pragma unroll
     for (int i = 0; i < R; ++i)
-        if (!(p.st[i]->done & p.skipmask)) live |= 1u << i;
+        if (i < nmem && !(p.st[mo + i]->done & p.skipmask)) live |= 1u << i;
     if (!live) return;
     const TA* __restrict__ A = p.A;
     const int64_t ld = p.ld, N = p.N;
-    const int Mv = p.Mv, KP = p.KP, nblk = p.nblk;
+    const int Mv = p.Mv, KP = p.KP;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nvec = Mv / VEC;
@@ -2173,6 +2177,10 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
     int ib = 0, cb = 0;
     const int64_t T = npair * nunit;
     int64_t ileft = T, cleft = T;
+    auto load = [](const VT* q) {
+        if constexpr (NT) return __builtin_nontemporal_load(q);
+        else return *q;
+    };
     auto issue = [&](VT(&b)[2][U]) {
         const int64_t c0 = 2 * iq, c1 = c0 + 1 < N ? c0 + 1 : N - 1;
         const VT* p0 = reinterpret_cast<const VT*>(A + c0 * ld);
@@ -2181,8 +2189,8 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int v = vb + u * kWave;
-            b[0][u] = __builtin_nontemporal_load(p0 + (v < nvec ? v : nvec - 1));
-            b[1][u] = __builtin_nontemporal_load(p1 + (v < nvec ? v : nvec - 1));
+            b[0][u] = load(p0 + (v < nvec ? v : nvec - 1));
+            b[1][u] = load(p1 + (v < nvec ? v : nvec - 1));
         }
         if (++ib == nunit) {
             ib = 0;
@@ -2205,7 +2213,7 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             if ((i & 1) != half) continue;
-            const double* __restrict__ r = p.r[i];
+            const double* __restrict__ r = p.r[mo + i];
             double* img = lds + (size_t)i * KP;
             double n2 = 0.0;
             for (int m0 = t; m0 < Mst; m0 += RP * kSweepThreads) {
@@ -2230,9 +2238,9 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
         for (int i = 0; i < R; ++i) {
             if (!(live & (1u << i))) continue;
             const double n2 = (n2s[0 * R + i] + n2s[1 * R + i]) + (n2s[2 * R + i] + n2s[3 * R + i]);
-            if (bid == 0 && tid == 0) p.st[i]->rnorm2 = n2;
+            if (bid == 0 && tid == 0) p.st[mo + i]->rnorm2 = n2;
             if (p.check_eps && !(sqrt(n2) >= p.eps)) {  // norm(residual!) >= eps || break  (:79,:132)
-                if (bid == 0 && tid == 0) p.st[i]->done |= STOP_EPS;
+                if (bid == 0 && tid == 0) p.st[mo + i]->done |= STOP_EPS;
                 live &= ~(1u << i);
             }
         }
@@ -2290,8 +2298,8 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
             }
             if constexpr (REFILL) {
                 const int v = vb + u * kWave;
-                b[0][u] = __builtin_nontemporal_load(p0 + (v < nvec ? v : nvec - 1));
-                b[1][u] = __builtin_nontemporal_load(p1 + (v < nvec ? v : nvec - 1));
+                b[0][u] = load(p0 + (v < nvec ? v : nvec - 1));
+                b[1][u] = load(p1 + (v < nvec ? v : nvec - 1));
             }
 #pragma unroll
             for (int j = 0; j < 2; ++j) {  // both columns of the pair against the same image values
@@ -2331,7 +2339,7 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
                 if (ccst >= 0) {
 #pragma unroll
                     for (int i = 0; i < R; ++i)
-                        if (live & (1u << i)) p.cvec[i][ccst] = cst[i];
+                        if (live & (1u << i)) p.cvec[mo + i][ccst] = cst[i];
                 }
                 ccst = -1;
                 cslot = 0;
@@ -2359,7 +2367,7 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
     if (ccst >= 0) {
 #pragma unroll
         for (int i = 0; i < R; ++i)
-            if (live & (1u << i)) p.cvec[i][ccst] = cst[i];
+            if (live & (1u << i)) p.cvec[mo + i][ccst] = cst[i];
     }
     if ((lane & 15) == 0) {
 #pragma unroll
@@ -2379,15 +2387,28 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
                 bv = rv[q];
                 bi = ri[q];
             }
-        p.pval[tid][bid] = bv;
-        p.pidx[tid][bid] = bi;
+        p.pval[mo + tid][bid] = bv;
+        p.pidx[mo + tid][bid] = bi;
     }
 }
 // U loads per column and unit, NB = 2 units in the ring
 template <typename TA, int U, int R>
 __global__ __launch_bounds__(kMultiThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_multi(const MultiSweep<TA> p) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    sweep_body_multi<TA, U, 2, R>(p, (int)blockIdx.x, lds);
+    sweep_body_multi<TA, U, 2, R>(p, (int)blockIdx.x, p.nblk, 0, R, lds);
+}
+// The WIDE pass: up to kWideMax members as two halves of n and n1 members.  The grid is a multiple of 16: workgroup b belongs to half
+// h = (b >> 3) & 1 and is stream s = (b >> 4) * 8 + (b & 7) of nblk / 2, so b and b ^ 8 walk exactly the same column pairs in the same
+// order, each against its own half's images.  Workgroups whose numbers differ by 8 have been observed on one XCD (nothing promises
+// it): the first request for a line of A should bring it into that XCD's L2 and the other half's request hit it, or join the miss in
+// flight: a pass of 4 + 4 fetches 1.08 times a narrow pass's bytes (FETCH_SIZE) and costs 1.33 narrow passes, not 2.
+// The halves never wait for each other; where they run, and when, changes the speed only.  Per member the arithmetic is the
+// narrow pass's; pval / pidx hold one partial per STREAM.  R is the larger half.
+template <typename TA, int U, int R, bool NT>
+__global__ __launch_bounds__(kMultiThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_wide(const MultiSweep<TA> p) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int b = (int)blockIdx.x, h = (b >> 3) & 1;
+    sweep_body_multi<TA, U, 2, R, NT>(p, (b >> 4) * 8 + (b & 7), p.nblk >> 1, h * kGroupMax, h ? p.n1 : p.n, lds);
 }
 
 // The shared sweep of round 7 (four waves, one column each, ring U / 32 / U as the single body's), kept for Float64 dictionaries:
@@ -2603,13 +2624,15 @@ __global__ __launch_bounds__(kSweepThreads) void k_sweep_multi_w4(const MultiSwe
 }
 
 // The append stages of two groups in ONE launch (the grouped scheduler's companion of k_tick's stages [0, 2G)): G workgroups per
-// k_qr2 member of group X, then G per k_qr1 member of group Y -- each signal's stage exactly as k_tick runs it.
+// k_qr2 member of group X, then G per k_qr1 member of group Y -- each signal's stage exactly as k_tick runs it.  (Up to kWideMax
+// members each: the groups of the wide pass.)
 template <typename TA>
 struct GroupAppend {
-    TickQr2 q2[kGroupMax];
-    TickQr1<TA> q1[kGroupMax];
+    TickQr2 q2[kWideMax];
+    TickQr1<TA> q1[kWideMax];
     int n2, n1;
 };
+static_assert(sizeof(GroupAppend<double>) <= 4096, "kernel arguments");
 template <typename TA>
 __global__ __launch_bounds__(kSweepThreads) void k_append_group(const GroupAppend<TA> a, const int G) {
     extern __shared__ __attribute__((aligned(16))) double lds[];

@@ -5,8 +5,8 @@
 #include <cstdint>
 #include <vector>
 
-// A pipeline holds three groups of signals (a group of the grouped schedule has up to sweep_group members, every other schedule's
-// one or none).  At tick n group n % 3 sweeps, group (n + 2) % 3 runs its k_qr1 stage and group (n + 1) % 3 its k_qr2 stage: every
+// A pipeline holds three groups of signals (a group of the grouped schedule has up to sweep_group members -- with wide groups up to
+// group_wide = 2 * sweep_group, swept as two halves --, every other schedule's one or none).  At tick n group n % 3 sweeps, group (n + 2) % 3 runs its k_qr1 stage and group (n + 1) % 3 its k_qr2 stage: every
 // signal's chain -- sweep, qr1, qr2 in three consecutive ticks -- takes one step in three ticks, k steps in 3k + 2 ticks.
 struct TickStages {
     int z, y, x;       // the sweep, qr1 and qr2 groups
@@ -41,11 +41,11 @@ struct PlanRound {
     PlanGroup g[2][3];  // [pipeline: 0 = A, the caller's context; 1 = B, the twin][group]; member m of group g is solver slot g + 3 m
 };
 
-// The rounds of a batch of nsig signals (R: the members a shared sweep serves, ctx->sweep_group).  Pairs: rounds of 3 + 3 while six or
+// The rounds of a batch of nsig signals (R: the members a shared pass serves, ctx->sweep_group or ctx->group_wide).  Pairs: rounds of 3 + 3 while six or
 // more signals remain, then 1 + 1, then a lone signal in the one-pipeline form.  Grouped: the fewest shared passes -- ceil(nsig / R)
 // groups of consecutive signals, their sizes as even as possible -- dealt six to a round, even offsets to A and odd ones to B; a last
 // round may leave B with no group and keeps the pair form.
-static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int R) {
+static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int R, bool one_pipe = false) {
     std::vector<PlanRound> rounds;
     auto round = [&](RoundForm form) -> PlanRound& {
         rounds.emplace_back();
@@ -84,9 +84,11 @@ static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int 
             if (nsig < 1 || R < 1) break;
             const int64_t ngroups = (nsig + R - 1) / R, base = nsig / ngroups, extra = nsig % ngroups;
             for (int64_t i = 0; i < ngroups; ++i) {
-                if (i % 6 == 0) round(RoundForm::Grouped);
+                const int per = one_pipe ? 3 : 6;  // (one_pipe, a measurement: three groups to a round, all on A; B stays empty)
+                if (i % per == 0) round(RoundForm::Grouped);
                 const int size = (int)(base + (i < extra ? 1 : 0));
-                rounds.back().g[i % 2][(i % 6) / 2] = {at, size};
+                if (one_pipe) rounds.back().g[0][i % 3] = {at, size};
+                else rounds.back().g[i % 2][(i % 6) / 2] = {at, size};
                 at += size;
             }
             break;

@@ -153,7 +153,8 @@ struct SpJob {
 
 constexpr int kPairTickGrid = 192;  // sweep workgroups of each of two pipelines side by side (measured: 176 -> 6.41e3, 192 -> 6.46e3, 224 -> 6.45e3, 256 -> 6.41e3 atoms/s)
 constexpr int kGroupTickGrid = 208;  // shared-sweep workgroups (k_sweep_multi, 8 waves) of each of two pipelines (measured at 4096 x 65536 f32, 18 signals: 160 -> 21.38e3, 171 -> 20.67e3, 192 -> 21.04e3, 205 -> 21.44e3, 208 -> 21.57e3, 216 -> 21.48e3 atoms/s)
-constexpr int kSlots = 3 * kGroupMax;  // solver slots of a context: three groups of the grouped batch scheduler (host/omp.hpp)
+constexpr int kWideTickGrid = 256;  // workgroups of a wide pass (k_sweep_wide: half as many column streams), a multiple of 16 (the pass alone, 4096 x 65536 f32, 3 + 3 members, default-policy loads: 128 -> 322.8, 160 -> 274.2, 192 -> 244.3, 208 -> 232.8, 224 -> 223.1, 240 -> 216.1, 256 -> 205.7 us; a narrow pass of three on 208: 167.1 us; the benchmark with both pipelines, 18 / 20 signals, atoms/s: 208 -> 24 784 / 26 232, 224 -> 25 129 / 26 767, 240 -> 25 258 / 27 060, 256 -> 26 087 / 27 622)
+constexpr int kSlots = 3 * kWideMax;  // solver slots of a context: three groups of the grouped batch scheduler (host/omp.hpp), wide groups of up to kWideMax
 struct csmp_ctx {
     SpJob spjob;  // the Subspace Pursuit solve this context is carrying (csmp_sp, csmp_sp_batch, the SP functor)
     std::shared_ptr<void> omprjob;  // the OMPR object of csmp_ompr / the OMPR functor (OmprJob, host/twostage.hpp), made on first use
@@ -196,7 +197,10 @@ struct csmp_ctx {
     int tune_fail_alloc = 0;    // csmp_tune (test hook): the n-th device allocation of a solver slot from now fails (dmalloc)
     int tune_pipelines = 0;  // csmp_tune: 1 = csmp_omp_batch keeps ONE pipeline of three signals, 2 = two side by side, 3 = two pipelines of three GROUPS (shared sweeps); 0 = automatic
     int tune_group_max = 0;  // csmp_tune: largest group of the grouped scheduler (0 = what the LDS holds, at most kGroupMax)
-    int sweep_group = 0;     // signals one shared sweep serves (configure_sweep; 0 where the sweep is phased or dynamic)
+    int sweep_group = 0;     // residual images of a shared sweep's workgroup (configure_sweep; 0 where the sweep is phased or dynamic)
+    int tune_group_wide = 0; // csmp_tune: 1 = no wide groups (the passes of up to sweep_group members only), 2 = wide groups three to a round on ONE pipeline (a measurement)
+    bool wide_refused = false;  // the device could not hold the wide groups' slots: groups of sweep_group until the dictionary or a csmp_tune value changes
+    int group_wide = 0;      // members one pass serves: kWideMax where wide groups are on (two halves of up to sweep_group = kGroupMax), else sweep_group
     int claim_pools = 8;     // counters a workgroup of the dynamic sweep finds empty in a row before it stops (its own, then the following workgroups')
     int tune_rebuild_direct = 0;  // csmp_tune: the oblivious start's Q'A pass reads its directions from L2 (k_fr_rebuild) instead of the LDS
     int tune_swap_refuse = 0;  // csmp_tune: OMPR's inverse-Gram exchanges fail their guard (tests walk the fallback to the QR path)
@@ -225,7 +229,7 @@ struct csmp_ctx {
     size_t sweep_lds_req = 0;    // the stand-alone sweep's LDS request when larger than sweep_lds (residency control)
     int tune_sweep_lds_kib = 0;  // csmp_tune
     Solver s;        // the ACTIVE solver slot (see activate_slot)
-    Solver park[kSlots];  // parked slots (park[active] is unused): three signals -- or three groups of up to kGroupMax -- are pipelined in csmp_omp_batch
+    Solver park[kSlots];  // parked slots (park[active] is unused): three signals -- or three groups of up to kWideMax -- are pipelined in csmp_omp_batch
     int active = 0;
     bool pipeline = true;
     int tick_nblk = 0;       // absolute override of the sweep workgroup count (CSMP_TICK_NBLK), 0 = per-CU rule

@@ -211,6 +211,11 @@ static int configure_sweep(csmp_ctx* ctx) {
         if (ctx->tune_group_max > 0) g = std::min(g, ctx->tune_group_max);
         ctx->sweep_group = g;
     }
+    // wide groups (k_sweep_wide): two workgroups, each with sweep_group = kGroupMax images, read the same bytes of A -- Float32, and only
+    // where nothing asked for smaller groups
+    ctx->wide_refused = false;
+    ctx->group_wide = ctx->sweep_group == kGroupMax && ctx->dtype == CSMP_F32 && ctx->tune_group_wide != 1 && ctx->tune_group_max == 0
+                          ? kWideMax : ctx->sweep_group;
     // short columns: the stand-alone sweep takes several columns per unit (k_sweep_short); the tick kernel keeps the one-column body
     // (the same bits).  Units of eight loads: eight columns of one chunk (two sets of four), four of two chunks, two of three or four
     // chunks.  csmp_tune(CSMP_TUNE_SWEEP_SHORT, 1): never.

@@ -301,6 +301,7 @@ static void pipe_begin(Pipe& p, csmp_ctx* c, const PlanGroup g[3], RoundForm for
     // those CUs) 160.4 us per tick; 16-chunk blocks on 176 workgroups (11/12 of the stand-alone sweep's optimum of 192) 162.6 us.
     p.nblk = pipe_nblk(c, form == RoundForm::One ? c->tick_grid : form == RoundForm::Grouped && c->dtype == CSMP_F32 ? kGroupTickGrid : kPairTickGrid);  // (tick_grid: configure_sweep)
     if (form == RoundForm::Grouped) {
+        p.nblk_wide = wide_nblk(c);
         p.lds = qr_lds;
         p.lds_sweep = excl;
     } else if (form == RoundForm::One || c->tune_pair_split == 1) {  // (pair_split 1, a measurement: the fused tick under the large request)
@@ -353,10 +354,13 @@ static int batch_impl(csmp_ctx* ctx, BatchIO& io, bool isfr, double eps, double 
     const BatchSchedule sched = batch_schedule(ctx, isfr, nsig, kc);
     const bool twin = sched == BatchSchedule::Pairs || sched == BatchSchedule::Grouped;
     const int nslots = sched == BatchSchedule::Grouped ? 3 * ctx->sweep_group : 3;
+    // wide groups: passes of up to group_wide members where the batch has more signals than a narrow pass serves, on 3 * group_wide slots
+    int members = ctx->sweep_group;
+    const int nslots_wide = sched == BatchSchedule::Grouped && ctx->group_wide > ctx->sweep_group && nsig > ctx->sweep_group && !ctx->wide_refused ? 3 * ctx->group_wide : 0;
     csmp_ctx* tw = nullptr;  // pipeline B's context: a clone of this one on its own stream
-    auto ensure_slots = [&](csmp_ctx* c, int from) -> int {
+    auto ensure_slots = [&](csmp_ctx* c, int from, int to) -> int {
         int r2 = CSMP_OK;
-        for (int q = from; q < nslots && r2 == CSMP_OK; ++q) {
+        for (int q = from; q < to && r2 == CSMP_OK; ++q) {
             activate_slot(c, q);
             r2 = solver_ensure(c, kc, (int)k);
             if (r2 == CSMP_OK && isfr) r2 = fr_ensure(c);
@@ -380,16 +384,44 @@ static int batch_impl(csmp_ctx* ctx, BatchIO& io, bool isfr, double eps, double 
         return CSMP_OK;
     };
     auto run_plan = [&]() -> int {  // (every way out of here once the twin exists passes the drain below)
-        CHECK(ensure_slots(ctx, 1));
+        CHECK(ensure_slots(ctx, 1, nslots));
         if (twin) {
             CHECK(twins_ensure(ctx, 1));
             tw = ctx->twins[0];
             tw->prof = ctx->prof;  // (csmp_profile_*: the second pipeline's launches are sampled like the first's)
             tw->prof_every = ctx->prof_every;
-            const int r2 = ensure_slots(tw, 0);
+            const int r2 = ensure_slots(tw, 0, nslots);
             if (r2 != CSMP_OK) {
                 ctx->err = tw->err;
                 return r2;
+            }
+            if (nslots_wide > 0) {
+                // the slots beyond the narrow groups': all of them on both contexts, or none -- a device that cannot hold them runs
+                // the groups of sweep_group members it has the slots for
+                csmp_ctx* cs[2] = {ctx, tw};
+                int r3 = CSMP_OK;
+                for (csmp_ctx* c : cs) {
+                    if (r3 != CSMP_OK) break;
+                    c->tune_fail_alloc = ctx->tune_fail_alloc;  // (the test hook counts on through the twin's allocations)
+                    r3 = ensure_slots(c, nslots, nslots_wide);
+                    ctx->tune_fail_alloc = c->tune_fail_alloc;
+                    if (c != ctx) c->tune_fail_alloc = 0;
+                }
+                if (r3 == CSMP_OK) {
+                    members = ctx->group_wide;
+                } else {
+                    ctx->wide_refused = true;  // (not tried again batch after batch: about a thousand allocations and two drains)
+                    for (csmp_ctx* c : cs) {
+                        (void)hipStreamSynchronize(c->stream);
+                        for (int q = nslots; q < nslots_wide; ++q) {
+                            activate_slot(c, q);
+                            solver_free(c->s);
+                        }
+                        activate_slot(c, 0);
+                        c->err.clear();
+                    }
+                    (void)hipGetLastError();
+                }
             }
             if (!ctx->ev_twin) HIPCHECK(hipEventCreateWithFlags(&ctx->ev_twin, hipEventDisableTiming));
             if (!tw->ev_twin) HIPCHECK(hipEventCreateWithFlags(&tw->ev_twin, hipEventDisableTiming));
@@ -397,7 +429,10 @@ static int batch_impl(csmp_ctx* ctx, BatchIO& io, bool isfr, double eps, double 
             HIPCHECK(hipEventRecord(ctx->ev_twin, ctx->stream));
             HIPCHECK(hipStreamWaitEvent(tw->stream, ctx->ev_twin, 0));
         }
-        for (const PlanRound& r : batch_plan(nsig, sched, ctx->sweep_group)) {
+        // Wide groups keep the plan's dealing over both pipelines (18 signals: groups 0 and 2 on A, 1 on B).  Measured on the benchmark,
+        // atoms/s at 18 / 20 signals, two runs each: 2 + 1 on 256 workgroups 26 087, 26 176 / 27 622, 27 735; three groups on ONE pipeline
+        // (csmp_tune group_wide 2) 25 257, 25 071 / 26 958, 27 060 -- its append launches have no other pipeline's sweep to run under.
+        for (const PlanRound& r : batch_plan(nsig, sched, members, members > ctx->sweep_group && ctx->tune_group_wide == 2)) {
             CHECK(each_member(r, init));
             CHECK(ctx->dtype == CSMP_F32 ? run_round<float>(r, ctx, tw, isfr, k, eps, p2) : run_round<double>(r, ctx, tw, isfr, k, eps, p2));
             CHECK(each_member(r, finish));

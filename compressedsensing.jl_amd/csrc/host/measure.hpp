@@ -123,11 +123,61 @@ extern "C" int csmp_live_resources(int64_t* device_bytes, int64_t* device_blocks
     return CSMP_OK;
 }
 
+// csmp_bench_sweep's variants 1 .. 3: the grouped scheduler's passes alone, back to back on one stream, as it launches them (grid,
+// LDS request of one workgroup per CU) on slots filled with the pseudo-random residual -- 1: the narrow pass (k_sweep_multi,
+// sweep_group members, kGroupTickGrid); 2: the wide pass (k_sweep_wide, twice sweep_group members, kWideTickGrid), nontemporal loads;
+// 3: the wide pass with default-policy loads.  csmp_tune's group_max and tick_grid set the members and the grid.
+template <typename TA>
+static int bench_shared_sweep(csmp_ctx* ctx, int variant, int reps, double* avg_ms) {
+    const int R = ctx->sweep_group, wide = variant >= 2;
+    if (R < 1) return fail(ctx, CSMP_ESTATE, "bench_sweep: no shared sweep for this dictionary");
+    if (wide && ctx->dtype != CSMP_F32) return fail(ctx, CSMP_ESTATE, "bench_sweep: the wide pass serves Float32 dictionaries");
+    const int members = wide ? 2 * R : R;
+    std::vector<double> r((size_t)ctx->M);
+    uint64_t sd = 0x9E3779B97F4A7C15ull;
+    int rc = CSMP_OK;
+    for (int m = 0; m < members && rc == CSMP_OK; ++m) {  // (slot 3 m: member m of group 0)
+        activate_slot(ctx, 3 * m);
+        rc = solver_ensure(ctx, 1, 1, false);
+        ctx->s.begun = false;
+        for (auto& v : r) {
+            sd = sd * 6364136223846793005ull + 1442695040888963407ull;
+            v = ((double)(sd >> 11) / 9007199254740992.0) - 0.5;
+        }
+        if (rc == CSMP_OK) rc = upload_b(ctx, r.data(), CSMP_F64);
+    }
+    activate_slot(ctx, 0);
+    CHECK(rc);
+    MultiSweep<TA> p;
+    p.A = (const TA*)ctx->dA; p.ld = ctx->ld; p.Mv = ctx->Mv; p.N = ctx->N;
+    p.eps = 0.0; p.check_eps = 0; p.skipmask = 0; p.KP = ctx->sweep_KP;
+    p.nblk = wide ? wide_nblk(ctx) : pipe_nblk(ctx, ctx->dtype == CSMP_F32 ? kGroupTickGrid : kPairTickGrid);
+    multi_members<TA>(ctx, p, 0, members);
+    const size_t lds = std::max(sweep_multi_lds_bytes(p.KP, p.n), (size_t)kPairLdsKiB * 1024);
+    auto launch = [&]() -> hipError_t { return wide ? wide_launch<TA>(ctx, p, lds, variant == 2) : multi_launch<TA>(ctx, p, lds); };
+    for (int i = 0; i < 3; ++i) HIPCHECK(launch());
+    struct Events {  // (released on every way out)
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    HIPCHECK(hipEventCreate(&ev.e[0]));
+    HIPCHECK(hipEventCreate(&ev.e[1]));
+    HIPCHECK(hipEventRecord(ev.e[0], ctx->stream));
+    for (int i = 0; i < reps; ++i) HIPCHECK(launch());
+    HIPCHECK(hipEventRecord(ev.e[1], ctx->stream));
+    HIPCHECK(hipStreamSynchronize(ctx->stream));
+    float ms0 = 0.f;
+    HIPCHECK(hipEventElapsedTime(&ms0, ev.e[0], ev.e[1]));
+    if (avg_ms) *avg_ms = (double)ms0 / reps;
+    return CSMP_OK;
+}
+
 extern "C" int csmp_bench_sweep(csmp_ctx* ctx, int variant, int reps, double* avg_ms) {
     if (!ctx || reps < 1) return CSMP_EINVAL;
     if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
-    if (variant != 0) return fail(ctx, CSMP_ESTATE, "bench_sweep: variant 0 (the product kernel) is the only one");
+    if (variant < 0 || variant > 3) return fail(ctx, CSMP_ESTATE, "bench_sweep: variant 0 (the product kernel), 1 (the shared pass), 2 (the wide pass) or 3 (the wide pass, default-policy loads)");
     HIPCHECK(hipSetDevice(ctx->dev));
+    if (variant != 0) return ctx->dtype == CSMP_F32 ? bench_shared_sweep<float>(ctx, variant, reps, avg_ms) : bench_shared_sweep<double>(ctx, variant, reps, avg_ms);
     CHECK(solver_ensure(ctx, 1, 1, false));
     ctx->s.begun = false;
     std::vector<double> r((size_t)ctx->M);
@@ -177,9 +227,18 @@ extern "C" int csmp_sweep_group(const csmp_ctx* ctx, int* group_max) {
     return CSMP_OK;
 }
 
+// members one pass of the grouped scheduler serves: 2 * group_max where wide groups are on (k_sweep_wide), else group_max
+extern "C" int csmp_sweep_group_wide(const csmp_ctx* ctx, int* group_wide) {
+    if (!ctx || !group_wide) return CSMP_EINVAL;
+    if (!ctx->dA) return CSMP_ESTATE;
+    *group_wide = ctx->group_wide;
+    return CSMP_OK;
+}
+
 extern "C" int csmp_tune(csmp_ctx* ctx, int key, int64_t value) {
     if (!ctx) return CSMP_EINVAL;
     if (value < 0 || value > (1 << 20)) return fail(ctx, CSMP_EINVAL, "csmp_tune: value out of range");
+    ctx->wide_refused = false;
     switch (key) {
         case CSMP_TUNE_SWEEP_GRID: ctx->tune_sweep_grid = (int)value; break;
         case CSMP_TUNE_SWEEP_UNIT:
@@ -211,6 +270,10 @@ extern "C" int csmp_tune(csmp_ctx* ctx, int key, int64_t value) {
         case CSMP_TUNE_GROUP_MAX:
             if (value > kGroupMax) return fail(ctx, CSMP_EINVAL, "csmp_tune: group_max must be 0 (what the LDS holds) or 1 .. 4");
             ctx->tune_group_max = (int)value;
+            break;
+        case CSMP_TUNE_GROUP_WIDE:
+            if (value > 2) return fail(ctx, CSMP_EINVAL, "csmp_tune: group_wide must be 0 (wide groups where they apply), 1 (off) or 2 (wide groups, three to a round on ONE pipeline)");
+            ctx->tune_group_wide = (int)value;
             break;
         case CSMP_TUNE_PIPELINES:
             if (value > 3) return fail(ctx, CSMP_EINVAL, "csmp_tune: pipelines must be 0 (automatic), 1, 2 or 3");

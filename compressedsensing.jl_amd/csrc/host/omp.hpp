@@ -77,6 +77,7 @@ struct Pipe {
     double eps = 0.0;     // omp's eps, fr's max_eps
     double min_d2 = 0.0;  // (fr)
     int nblk = 0;         // sweep workgroups
+    int nblk_wide = 0;    // workgroups of a wide pass (groups of more than kGroupMax members): a multiple of 16, nblk_wide / 2 column streams
     int U = 8;            // (fr: the sweep's block size)
     size_t lds = 0;       // the request of the launch that carries the append stages (and the sweep, where lds_sweep == 0)
     size_t lds_sweep = 0; // > 0: the sweep is a launch of its own and asks for at least this
@@ -96,6 +97,8 @@ static int pipe_nblk(const csmp_ctx* ctx, int64_t grid) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ctx->tick_nblk > 0 ? ctx->tick_nblk : grid, groups),
                                                       ctx->prop.multiProcessorCount * 8 + 8));
 }
+// the workgroups of a wide pass: kWideTickGrid or the csmp_tune override, under pipe_nblk's limits, rounded down to a multiple of 16
+static int wide_nblk(const csmp_ctx* ctx) { return std::max(16, pipe_nblk(ctx, kWideTickGrid) / 16 * 16); }
 
 // one tick of a pipeline of three signals (k_tick): the sweep of one, the qr1 and qr2 stages of the other two
 template <typename TA>
@@ -169,6 +172,51 @@ static hipError_t multi_launch_u(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t 
         default: return multi_launch_t<TA, U, 4>(ctx, p, lds);
     }
 }
+// The wide pass (k_sweep_wide, Float32): p.n + p.n1 members on p.nblk workgroups, a multiple of 16; R is the larger half, p.n.
+// nt: the ring's loads nontemporal; kWideNt is what the scheduler runs.  Default-policy loads: a nontemporal load gives up the reuse
+// the second half lives on (csmp_bench_sweep variants 2 / 3 against 1, 4096 x 65536 f32, grid 256, a narrow pass = 1: 4 + 4 members
+// nt 1.58, default 1.33; 3 + 3 members nt 1.54, default 1.23 -- profiles/r09_wide_sweep.txt).
+template <typename TA, bool NT>
+static hipError_t wide_launch_nt(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t lds) {
+    if constexpr (Vec<TA>::n == 2) return hipErrorInvalidValue;  // (Float64 dictionaries keep groups of kGroupMax)
+    else {
+        auto go = [&](auto kern) {
+            if (lds > 64 * 1024) {
+                hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) return e;
+            }
+            hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(kMultiThreads), lds, ctx->stream, p);
+            return hipGetLastError();
+        };
+        if (p.nblk < 16 || p.nblk % 16 != 0 || p.n1 < 1 || p.n1 > p.n || p.n > kGroupMax) return hipErrorInvalidValue;
+        switch (p.n) {
+            case 1: return go(k_sweep_wide<TA, 4, 1, NT>);
+            case 2: return go(k_sweep_wide<TA, 4, 2, NT>);
+            case 3: return go(k_sweep_wide<TA, 4, 3, NT>);
+            default: return go(k_sweep_wide<TA, 4, 4, NT>);
+        }
+    }
+}
+constexpr bool kWideNt = false;
+template <typename TA>
+static hipError_t wide_launch(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t lds, bool nt = kWideNt) {
+    return nt ? wide_launch_nt<TA, true>(ctx, p, lds) : wide_launch_nt<TA, false>(ctx, p, lds);
+}
+// the members [first, first + size) step 3 of the slots from slot0 as a pass's entries: up to kGroupMax of them the narrow pass's
+// [0, n); more, the wide pass's halves [0, n) and [kGroupMax, kGroupMax + n1).  Entries past a half's members repeat its last one
+// (the narrow pass never reads them; the wide pass stages their image and masks them).
+template <typename TA>
+static void multi_members(csmp_ctx* ctx, MultiSweep<TA>& p, int slot0, int size) {
+    const bool wide = size > kGroupMax;
+    p.n = wide ? (size + 1) / 2 : size;
+    p.n1 = wide ? size / 2 : 0;
+    for (int e = 0; e < kWideMax; ++e) {
+        const int h = e / kGroupMax, i = e % kGroupMax;
+        const int m = h == 0 || !wide ? std::min(i, p.n - 1) : p.n + std::min(i, p.n1 - 1);
+        const Solver& s = *slot_ptr(ctx, slot0 + 3 * m);
+        p.r[e] = s.r; p.cvec[e] = s.cvec; p.pval[e] = s.pval; p.pidx[e] = s.pidx; p.st[e] = s.st;
+    }
+}
 // Float32: the 512-thread pair body, whose unit is its own (4 loads per column); Float64: the four-wave body on ctx->sweep_U
 template <typename TA>
 static hipError_t multi_launch(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t lds) {
@@ -197,7 +245,7 @@ static int group_pipe_launch(Pipe& gp, int64_t n) {
         for (int m = 0; m < a.n1; ++m) {
             Solver& s = *slot_ptr(ctx, t.y + 3 * m);
             const int jh1 = qr1_advance(s);
-            a.q1[m] = tick_qr1_params<TA>(ctx, s, skip, gp.nblk, jh1, 1);
+            a.q1[m] = tick_qr1_params<TA>(ctx, s, skip, a.n1 > kGroupMax ? gp.nblk_wide / 2 : gp.nblk, jh1, 1);  // (the sweep's partials: one per stream)
         }
         const int G = ctx->s.G;
         auto kern = k_append_group<TA>;
@@ -208,16 +256,14 @@ static int group_pipe_launch(Pipe& gp, int64_t n) {
     if (t.az) {
         MultiSweep<TA> p;
         p.A = (const TA*)ctx->dA; p.ld = ctx->ld; p.Mv = ctx->Mv; p.N = ctx->N;
-        p.eps = gp.eps; p.check_eps = t.tz > 0 ? 1 : 0; p.skipmask = skip; p.nblk = gp.nblk; p.KP = ctx->sweep_KP;
-        p.n = gp.size[t.z];
-        for (int m = 0; m < kGroupMax; ++m) {
-            const Solver& s = *slot_ptr(ctx, t.z + 3 * std::min(m, p.n - 1));  // (entries past n are never read)
-            p.r[m] = s.r; p.cvec[m] = s.cvec; p.pval[m] = s.pval; p.pidx[m] = s.pidx; p.st[m] = s.st;
-        }
+        const bool wide = gp.size[t.z] > kGroupMax;  // (more members than a workgroup has images: two workgroups per read of A)
+        p.eps = gp.eps; p.check_eps = t.tz > 0 ? 1 : 0; p.skipmask = skip; p.nblk = wide ? gp.nblk_wide : gp.nblk; p.KP = ctx->sweep_KP;
+        multi_members<TA>(ctx, p, t.z, gp.size[t.z]);
         // ONE sampled launch per shared pass: it reads A once, whatever the group size
         const bool timed = prof_pick(ctx);
         if (timed) CHECK(prof_mark(ctx));
-        HIPCHECK(multi_launch<TA>(ctx, p, std::max(sweep_multi_lds_bytes(p.KP, p.n), gp.lds_sweep)));
+        const size_t lds = std::max(sweep_multi_lds_bytes(p.KP, p.n), gp.lds_sweep);
+        HIPCHECK(wide ? wide_launch<TA>(ctx, p, lds) : multi_launch<TA>(ctx, p, lds));
         if (timed) CHECK(prof_mark(ctx));
     }
     return CSMP_OK;

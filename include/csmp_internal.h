@@ -27,7 +27,10 @@ int csmp_profile_overhead(csmp_ctx *ctx, int reps, double *avg_ms);
 int csmp_live_resources(int64_t *device_bytes, int64_t *device_blocks, int64_t *pinned_bytes, int64_t *registered_ranges, int64_t *events,
                         int64_t *streams);
 /* sweep bandwidth probe: `reps` product sweeps (argmaxinner!(P), src/matchingpursuit.jl:181-185) of a random residual,
- * bracketed by one HIP event pair on the ctx stream; returns the average ms per sweep.  variant must be 0. */
+ * bracketed by one HIP event pair on the ctx stream; returns the average ms per sweep.  variant 0: the product kernel.  Variants
+ * 1 .. 3 time the passes of csmp_omp_batch's grouped scheduler alone, as it launches them -- 1: the shared pass of group_max residuals
+ * (k_sweep_multi); 2: the wide pass of 2 * group_max residuals (k_sweep_wide, Float32), nontemporal loads; 3: the wide pass with
+ * default-policy loads.  CSMP_TUNE_GROUP_MAX and CSMP_TUNE_TICK_GRID set their members and grid. */
 int csmp_bench_sweep(csmp_ctx *ctx, int variant, int reps, double *avg_ms);
 /* what configure_sweep chose for the resident dictionary: loads per unit of k_sweep_gen (16 / 8 / 4); phases the residual is
  * staged in (1: one LDS image); workgroups of a stand-alone sweep and of the sweep inside the tick kernel; dynamic LDS bytes;
@@ -38,6 +41,9 @@ int csmp_sweep_config(const csmp_ctx *ctx, int *unit_loads, int *phases, int *wo
 /* signals one shared sweep of csmp_omp_batch's grouped scheduler serves for the resident dictionary (k_sweep_multi: one LDS image of
  * the residual per signal, at most 4); 0 = no shared sweep for this dictionary (a phased or dynamic sweep): that scheduler is not used */
 int csmp_sweep_group(const csmp_ctx *ctx, int *group_max);
+/* signals one PASS of that scheduler serves: 2 * group_max where wide groups are on (k_sweep_wide: two workgroups with group_max images
+ * each read the same bytes of A), else group_max */
+int csmp_sweep_group_wide(const csmp_ctx *ctx, int *group_wide);
 /* measurement overrides of that choice, applied to the resident dictionary at once and to later ones: 0 = automatic */
 #define CSMP_TUNE_SWEEP_GRID 2   /* workgroups of the product sweep */
 #define CSMP_TUNE_SWEEP_UNIT 3   /* loads per unit (16, 8 or 4) */
@@ -45,6 +51,7 @@ int csmp_sweep_group(const csmp_ctx *ctx, int *group_max);
 #define CSMP_TUNE_SWEEP_DYN 9     /* 1: the product sweep hands its columns out at run time (k_sweep_dyn; one LDS image, grids up to 512 workgroups); n = 2..64: only the last 1 / n of a workgroup's columns, after a static head; default 0: the static split */
 #define CSMP_TUNE_PIPELINES 12    /* 1: csmp_omp_batch keeps one pipeline of three signals; 2: two pipelines side by side whatever the sizes (rounds of 3 + 3 signals, the remainder 1 + 1); 3: two pipelines of three GROUPS of signals, each group's sweeps one shared pass over A (k_sweep_multi); default 0: 3 where a shared pass serves two or more signals, else 2, from two signals and a 4-MiB dictionary on; 3 falls back to 2 where no shared sweep exists */
 #define CSMP_TUNE_GROUP_MAX 20    /* largest group of the grouped scheduler (CSMP_TUNE_PIPELINES 3); 0 = as many residual images as the LDS holds, at most 4 */
+#define CSMP_TUNE_GROUP_WIDE 21   /* 1: no wide groups (every pass serves at most group_max signals); 2: wide groups, the three of a round on ONE pipeline (a measurement: slower); default 0: batches of more signals than that run groups of up to 2 * group_max wherever the grouped scheduler has group_max = 4 images per workgroup on a Float32 dictionary and CSMP_TUNE_GROUP_MAX is 0.  CSMP_TUNE_TICK_GRID overrides the wide pass's grid too, rounded down to a multiple of 16 */
 #define CSMP_TUNE_TICK_ORDER 10   /* 1: the tick kernel's sweep workgroups are dispatched ahead of its append stages' */
 #define CSMP_TUNE_CLAIM_POOLS 11  /* the dynamic sweep: column pools a workgroup may claim from (its own first) */
 #define CSMP_TUNE_PAIR_LDS_KIB 13 /* dynamic LDS (KiB) requested by the ticks of two pipelines side by side: above 80 = one workgroup per CU (default 81), 1 = what the kernels need */

@@ -179,11 +179,12 @@ static void tick_rotation() {
 }
 
 // every plan of nsig 1..64 signals: each signal in exactly one (round, pipeline, group, member), the members of a group consecutive,
-// no solver slot at or above 3 * kGroupMax (= kSlots, host/ctx.hpp), and the round shapes of each schedule
+// no solver slot at or above 3 * kWideMax (= kSlots, host/ctx.hpp), and the round shapes of each schedule.  R: the members of a
+// pass, up to 8 with wide groups (two halves of up to four).
 static void batch_plans() {
-    const int kSlots = 3 * 4;
+    const int kSlots = 3 * 8;
     for (int64_t nsig = 1; nsig <= 64; ++nsig)
-        for (int R = 1; R <= 4; ++R)
+        for (int R = 1; R <= 8; ++R)
             for (BatchSchedule sched : {BatchSchedule::Signals, BatchSchedule::One, BatchSchedule::Pairs, BatchSchedule::Grouped}) {
                 const std::vector<PlanRound> plan = batch_plan(nsig, sched, R);
                 if (sched == BatchSchedule::Signals) {
