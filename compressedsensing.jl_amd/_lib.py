@@ -65,6 +65,7 @@ SIGNATURES = {
     "csmp_foba": (C.c_int, [vp, vp, C.c_int, C.c_double, i64, vp, vp, C.POINTER(i64)]),
     "csmp_br": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_double, i64, C.c_int, vp, vp, C.POINTER(i64)]),
     "csmp_fr_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, i64, C.c_double, C.c_double, vp, vp, vp, C.c_int]),
+    "csmp_mp_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, i64, vp, vp, vp, C.c_int]),
     "csmp_ompr": (C.c_int, [vp, vp, C.c_int, i64, C.c_double, i64, vp, vp, C.POINTER(i64), C.POINTER(i64)]),
     "csmp_omp_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, i64, C.c_double, vp, vp, vp, C.c_int]),
     "csmp_gomp_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, i64, i64, C.c_double, vp, vp, vp, C.c_int]),
@@ -461,6 +462,14 @@ class Context:
         """torch CUDA tensors: B (nsig, M) rows = signals; outputs idx (nsig, k) int64,
         val (nsig, k) float64, nnz (nsig,) int64.  Only enqueues work; call sync()."""
         self._batch_device("csmp_omp_batch", B, k, (i64(int(k)), C.c_double(eps)), idx, val, nnz)
+
+    def mp_batch(self, B, k):
+        """mp for every column of the host matrix B (M x nsig, column-major) -> (idx k x nsig, val, nnz); nnz[s] <= k: atoms repeat."""
+        return self._batch_host("csmp_mp_batch", B, k, (i64(int(k)),))
+
+    def mp_batch_device(self, B, k, idx, val, nnz):
+        """torch CUDA tensors as in omp_batch_device.  Only enqueues work; call sync()."""
+        self._batch_device("csmp_mp_batch", B, k, (i64(int(k)),), idx, val, nnz)
 
     def gomp_batch(self, B, l, k, eps):
         """Host matrix B (M x nsig, column-major) -> (idx k x nsig, val, nnz): gomp for every column, two solves in flight."""

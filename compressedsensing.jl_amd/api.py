@@ -285,6 +285,18 @@ def omp_batch(A, B, k, eps=None):
             D.close()
 
 
+def mp_batch(A, B, k):
+    """[mp(A, B[:, s], k) for s in axes(B, 2)] on one GPU, x starting from 0 (up to eight signals share each pass over the dictionary):
+    list of SparseVectors.  Warm starts stay with mp."""
+    D, tmp = _dict(A)
+    try:
+        idx, val, nnz = D.ctx.mp_batch(B, int(k))
+        return [SparseVector(D.shape[1], idx[:n, s].copy(), val[:n, s].copy()) for s, n in enumerate(nnz)]
+    finally:
+        if tmp:
+            D.close()
+
+
 def gomp_batch(A, B, l, k, eps=None):
     """[gomp(A, B[:, s], l, eps, k) for s in axes(B, 2)] on one GPU (two solves in flight): list of SparseVectors."""
     eps = _meta(A)[2] if eps is None else eps

@@ -42,6 +42,7 @@ using namespace csmp;
 #include "host/batch_io.hpp"
 #include "host/omp.hpp"
 #include "host/forward.hpp"
+#include "host/mp_batch.hpp"
 #include "host/steps_sharding.hpp"
 #include "host/removal.hpp"
 #include "host/gomp_sp.hpp"

@@ -2980,6 +2980,119 @@ __global__ __launch_bounds__(256) void k_mp_update(const TA* __restrict__ A, int
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Matching pursuit for the members of one group of csmp_mp_batch (host/mp_batch.hpp): the step that follows a shared pass
+// (k_sweep_multi / k_sweep_wide), ONE launch for all members -- k_select (mode 0) and k_mp_update of every member at once.
+// Member m owns wgs = ceil(M / 256) workgroups.  Each of them reduces the pass's nblk[m] partials ITSELF with better() -- the
+// lexicographic order k_select uses, so every workgroup of a member finds the same atom --, reads c = cvec[i] and updates its own 256
+// rows with k_mp_update's expression.  Workgroup 0 of the member appends (i, c) to the member's log (sel, z) and advances the
+// control block; no workgroup reads what another workgroup of the same launch writes (pval / pidx / cvec are the pass's, r is
+// touched row by row, the control block by workgroup 0 of its member alone).
+struct MpGroup {
+    int n;  // members
+    double* r[kWideMax];
+    const double* cvec[kWideMax]; const double* pval[kWideMax]; const int* pidx[kWideMax];
+    int nblk[kWideMax];  // partials the member's pass left: one per workgroup of a narrow pass, one per stream of a wide one
+    DevState* st[kWideMax]; int* sel[kWideMax]; double* z[kWideMax];
+    int cap[kWideMax];   // entries the member's log holds
+};
+template <typename TA>
+__global__ __launch_bounds__(256) void k_mp_group(const TA* __restrict__ A, int64_t ld, int M, int64_t N, const MpGroup g, int wgs) {
+    __shared__ double sv[256];
+    __shared__ int si[256];
+    const int m = (int)blockIdx.x / wgs, w = (int)blockIdx.x % wgs, tid = threadIdx.x;
+    if (m >= g.n) return;
+    const double* __restrict__ pval = g.pval[m];
+    const int* __restrict__ pidx = g.pidx[m];
+    const int nblk = g.nblk[m];
+    double bv = -1.0;
+    int bi = 0x7fffffff;
+    for (int q = tid; q < nblk; q += 256)
+        if (better(pval[q], pidx[q], bv, bi)) {
+            bv = pval[q];
+            bi = pidx[q];
+        }
+    block_argmax(bv, bi, sv, si);
+    if (bi < 0 || bi >= N) bi = 0;  // (no partial won: a residual of NaNs.  Atom 0 and its NaN, never an address outside A)
+    const double c = g.cvec[m][bi];
+    double* __restrict__ r = g.r[m];
+    const int row = w * 256 + tid;
+    if (row < M) r[row] = fma(-(double)A[(int64_t)bi * ld + row], c, r[row]);
+    if (w == 0 && tid == 0) {
+        DevState* st = g.st[m];
+        const int j = st->nsel;
+        if (j < g.cap[m]) {
+            g.sel[m][j] = bi;
+            g.z[m][j] = c;
+            st->nsel = j + 1;
+        }
+        st->cand = bi;
+        st->cval = c;
+        st->j = j;
+        st->go = 1;
+        st->steps += 1;
+    }
+}
+
+// The log of a Matching Pursuit solve -> its SparseVector, on the device (mp_collect's rule, host/forward.hpp): ascending atoms, the
+// increments of one atom added in step order, no entry for an atom whose increments were all exactly zero.  One workgroup per
+// signal.  The entry of an atom is produced by the thread that holds the atom's FIRST step: it adds the atom's increments in step
+// order (0.0 + d is d, so the sum is the one "x[i] += d" builds) and ranks the atom among the kept ones -- a stable counting sort with
+// the log left in global memory, so the number of steps is not bound by the LDS (n^2 / 256 comparisons per thread: 256 steps take a
+// few microseconds, once per solve).  keep / acc: n words of scratch each.  Unused tails: -1 and 0.
+struct MpEmit {
+    int n;  // signals
+    const int* sel[kWideMax]; const double* z[kWideMax]; const DevState* st[kWideMax];
+    int* keep[kWideMax]; double* acc[kWideMax];
+    int64_t* idx[kWideMax]; double* val[kWideMax]; int64_t* nnz[kWideMax];
+};
+__global__ __launch_bounds__(256) void k_mp_emit(const MpEmit e, int outcap) {
+    __shared__ int cnt;
+    const int m = (int)blockIdx.x, tid = threadIdx.x;
+    if (m >= e.n) return;
+    const int* __restrict__ sel = e.sel[m];
+    const double* __restrict__ z = e.z[m];
+    int* keep = e.keep[m];
+    double* acc = e.acc[m];
+    const int n = min(e.st[m]->nsel, outcap);
+    if (tid == 0) cnt = 0;
+    for (int t = tid; t < n; t += 256) {
+        const int a = sel[t];
+        bool first = true, any = false;
+        double s = 0.0;
+        for (int u = 0; u < n; ++u) {
+            if (sel[u] != a) continue;
+            if (u < t) {
+                first = false;
+                break;
+            }
+            s += z[u];
+            any = any || z[u] != 0.0;
+        }
+        keep[t] = first && any ? 1 : 0;
+        acc[t] = s;
+    }
+    __syncthreads();
+    int64_t* __restrict__ idx = e.idx[m];
+    double* __restrict__ val = e.val[m];
+    for (int t = tid; t < n; t += 256) {
+        if (!keep[t]) continue;
+        const int a = sel[t];
+        int rank = 0;
+        for (int u = 0; u < n; ++u) rank += (keep[u] && sel[u] < a) ? 1 : 0;
+        idx[rank] = a;
+        val[rank] = acc[t];
+        atomicAdd(&cnt, 1);
+    }
+    __syncthreads();
+    const int nn = cnt;
+    for (int q = nn + tid; q < outcap; q += 256) {
+        idx[q] = -1;
+        val[q] = 0.0;
+    }
+    if (tid == 0) *e.nnz[m] = nn;
+}
+
 // out[t] = c[idx[t]] (OMPR reads the correlations of its support, src/twostage.jl:165)
 __global__ __launch_bounds__(256) void k_gather(const double* __restrict__ c, const int* __restrict__ idx, int n,
                                                 double* __restrict__ out) {

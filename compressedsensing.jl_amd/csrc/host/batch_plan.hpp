@@ -96,3 +96,32 @@ static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int 
     }
     return rounds;
 }
+
+// The rounds of csmp_mp_batch (host/mp_batch.hpp): a round is ONE group per pipeline -- MP has no append stages to rotate, a step of
+// a group is its shared pass and one short launch --, up to 2 R signals (R: the members a pass serves).  The fewest passes:
+// ceil(nsig / R) groups of consecutive signals, their sizes as even as possible, dealt two to a round, A then B.  one_pipe: every
+// round holds one group, on A.  split_lone: a round that would hold a single group of two or more signals on A -- a batch of up to R
+// signals, the last round of an odd number of groups -- is cut into two halves, A's the larger, so that each half's short launch
+// falls under the other's pass (one pass more; kMpSplitLone, host/mp_batch.hpp, says which was faster).
+struct MpRound {
+    PlanGroup g[2];  // [pipeline: 0 = A, the caller's context; 1 = B, the twin]; member m of a group is solver slot 3 m
+};
+static std::vector<MpRound> mp_batch_plan(int64_t nsig, int R, bool one_pipe, bool split_lone) {
+    std::vector<MpRound> rounds;
+    if (nsig < 1 || R < 1) return rounds;
+    const int64_t ngroups = (nsig + R - 1) / R, base = nsig / ngroups, extra = nsig % ngroups;
+    int64_t at = 0;
+    for (int64_t i = 0; i < ngroups; ++i) {
+        const int size = (int)(base + (i < extra ? 1 : 0));
+        if (one_pipe || i % 2 == 0) rounds.emplace_back();
+        MpRound& r = rounds.back();
+        if (!one_pipe && split_lone && i % 2 == 0 && i + 1 == ngroups && size >= 2) {
+            r.g[0] = {at, (size + 1) / 2};
+            r.g[1] = {at + (size + 1) / 2, size / 2};
+        } else {
+            r.g[one_pipe ? 0 : i % 2] = {at, size};
+        }
+        at += size;
+    }
+    return rounds;
+}

@@ -440,6 +440,18 @@ omp_batch(A::MatOrDict, B::StridedMatrix, ε::Real, k::Int; kw...) = begin
     [to_sparse(size(A, 2), idx[:, s], val[:, s], nnz[s]) for s in 1:size(B, 2)]
 end
 
+# [mp(A, B[:, s], k) for s in axes(B, 2)], x starting from 0: up to eight signals share each pass over A (csmp_mp_batch)
+function mp_batch(A::MatOrDict{T}, B::StridedMatrix, k::Int) where {T}
+    D = dict(A)
+    BB = eltype(B) <: Union{Float32,Float64} ? B : convert(Matrix{Float64}, B)
+    nsig = size(BB, 2)
+    idx, val, nnz = fill(Int64(-1), k, nsig), zeros(Float64, k, nsig), zeros(Int64, nsig)
+    GC.@preserve BB idx val nnz check(D, ccall((:csmp_mp_batch, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}, Cint),
+        D.ctx, BB, dtype_code(eltype(BB)), stride(BB, 2), nsig, CSMP_HOST, k, idx, val, nnz, CSMP_HOST))
+    [to_sparse(size(A, 2), idx[:, s], val[:, s], nnz[s]) for s in 1:nsig]
+end
+
 # [gomp(A, B[:, s], l, eps, k) for s in axes(B, 2)]: two solves in flight on two streams (csmp_gomp_batch)
 function gomp_batch(A::MatOrDict{T}, B::StridedMatrix, l::Int, ε::Real, k::Int) where {T}
     D = dict(A)

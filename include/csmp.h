@@ -191,6 +191,19 @@ int csmp_omp_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64
 int csmp_fr_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k,
                   double max_eps, double min_delta, int64_t *idx, double *val, int64_t *nnz, int out_loc);
 
+/* mp(A, B[:,s], k) for s = 0..nsig-1 (src/matchingpursuit.jl:26-40 in the caller's loop), x starting from 0: the conventions of
+ * csmp_omp_batch (B on host or device, idx / val: k x nsig with unused tails -1 / 0, nnz: nsig, outputs on host or device).  Every
+ * signal takes k steps; atoms may repeat, so nnz[s] <= k.  Signal s's output is csmp_mp's, bit for bit: ascending atoms, the
+ * increments of one atom added in step order, no entry for an atom whose increments were all exactly zero.  No factorisation is
+ * kept, so k is bound neither by M nor by the append kernels' capacity.  Warm starts stay with csmp_mp.
+ * Up to eight signals (Float32 dictionaries; four on Float64) share ONE pass over the dictionary per step, and two such groups run
+ * side by side on two streams; with out_loc == CSMP_DEVICE the call only enqueues work (csmp_sync).  The signals go one after the
+ * other through csmp_mp's own launches -- same results, no gain -- where the resident dictionary has no shared pass (columns
+ * longer than the LDS holds, i.e. phased sweeps, and the internal dynamic-sweep measurement switch), with CSMP_OPT_SCREENED_SWEEP
+ * on, with CSMP_OPT_PIPELINE 0, and for nsig == 1.  nsig == 0 returns CSMP_OK and touches nothing. */
+int csmp_mp_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k, int64_t *idx,
+                  double *val, int64_t *nnz, int out_loc);
+
 /* gomp(A, B[:,s], l, eps, k) for s = 0..nsig-1 (src/matchingpursuit.jl:116-139 in the caller's loop), 1 <= l <= k: the conventions
  * of csmp_omp_batch (idx / val: k x nsig).  TWO solves are in flight, one on the context's stream and one on an internal clone's,
  * out of phase: a signal's short stages (top-l selection, the l-column panel append) run under the other signal's dictionary

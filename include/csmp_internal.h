@@ -49,7 +49,7 @@ int csmp_sweep_group_wide(const csmp_ctx *ctx, int *group_wide);
 #define CSMP_TUNE_SWEEP_UNIT 3   /* loads per unit (16, 8 or 4) */
 #define CSMP_TUNE_TICK_GRID 4    /* sweep workgroups inside the tick kernel of csmp_omp_batch */
 #define CSMP_TUNE_SWEEP_DYN 9     /* 1: the product sweep hands its columns out at run time (k_sweep_dyn; one LDS image, grids up to 512 workgroups); n = 2..64: only the last 1 / n of a workgroup's columns, after a static head; default 0: the static split */
-#define CSMP_TUNE_PIPELINES 12    /* 1: csmp_omp_batch keeps one pipeline of three signals; 2: two pipelines side by side whatever the sizes (rounds of 3 + 3 signals, the remainder 1 + 1); 3: two pipelines of three GROUPS of signals, each group's sweeps one shared pass over A (k_sweep_multi); default 0: 3 where a shared pass serves two or more signals, else 2, from two signals and a 4-MiB dictionary on; 3 falls back to 2 where no shared sweep exists */
+#define CSMP_TUNE_PIPELINES 12    /* 1: csmp_omp_batch keeps one pipeline of three signals; 2: two pipelines side by side whatever the sizes (rounds of 3 + 3 signals, the remainder 1 + 1); 3: two pipelines of three GROUPS of signals, each group's sweeps one shared pass over A (k_sweep_multi); default 0: 3 where a shared pass serves two or more signals, else 2, from two signals and a 4-MiB dictionary on; 3 falls back to 2 where no shared sweep exists.  csmp_mp_batch: 1 keeps one stream, 2 and 3 take two whatever the size; a round with a single group runs its halves on the two streams under 2 and the whole group on one under 3 */
 #define CSMP_TUNE_GROUP_MAX 20    /* largest group of the grouped scheduler (CSMP_TUNE_PIPELINES 3); 0 = as many residual images as the LDS holds, at most 4 */
 #define CSMP_TUNE_GROUP_WIDE 21   /* 1: no wide groups (every pass serves at most group_max signals); 2: wide groups, the three of a round on ONE pipeline (a measurement: slower); default 0: batches of more signals than that run groups of up to 2 * group_max wherever the grouped scheduler has group_max = 4 images per workgroup on a Float32 dictionary and CSMP_TUNE_GROUP_MAX is 0.  CSMP_TUNE_TICK_GRID overrides the wide pass's grid too, rounded down to a multiple of 16 */
 #define CSMP_TUNE_TICK_ORDER 10   /* 1: the tick kernel's sweep workgroups are dispatched ahead of its append stages' */

@@ -249,6 +249,44 @@ static void batch_plans() {
             }
 }
 
+// every plan csmp_mp_batch can get for nsig 1..64 (host/batch_plan.hpp: mp_batch_plan): each signal in exactly one group, the groups
+// consecutive and in order (A's, then B's, round by round), none above its cap R, the fewest passes unless a lone group is split,
+// B empty on one pipeline, and no round of two pipelines with a group on B only
+static void mp_batch_plans() {
+    for (int64_t nsig = 1; nsig <= 64; ++nsig)
+        for (int R = 1; R <= 8; ++R)
+            for (int mode = 0; mode < 4; ++mode) {
+                const bool one_pipe = (mode & 1) != 0, split = (mode & 2) != 0;
+                const std::vector<MpRound> plan = mp_batch_plan(nsig, R, one_pipe, split);
+                std::vector<int> seen((size_t)nsig, 0);
+                const int64_t ngroups = (nsig + R - 1) / R;
+                int64_t next = 0, groups = 0;
+                for (size_t j = 0; j < plan.size(); ++j) {
+                    const MpRound& r = plan[j];
+                    EXPECT(r.g[0].size >= 1);  // (a round always has a group on A)
+                    if (one_pipe) EXPECT(r.g[1].size == 0);
+                    for (int p = 0; p < 2; ++p) {
+                        const PlanGroup& G = r.g[p];
+                        EXPECT(G.size >= 0 && G.size <= R && 3 * (G.size - 1) < 3 * 8);
+                        if (G.size == 0) continue;
+                        EXPECT(G.first == next);
+                        for (int m = 0; m < G.size; ++m)
+                            if (G.first + m >= 0 && G.first + m < nsig) seen[(size_t)(G.first + m)] += 1;
+                        next += G.size;
+                        groups += 1;
+                    }
+                    if (!one_pipe && j + 1 < plan.size()) EXPECT(r.g[1].size >= 1);  // (only the last round may leave B idle)
+                    if (!one_pipe && r.g[1].size > 0) EXPECT(r.g[0].size - r.g[1].size >= 0 && r.g[0].size - r.g[1].size <= 1);
+                }
+                EXPECT(next == nsig);
+                for (int64_t s = 0; s < nsig; ++s) EXPECT(seen[(size_t)s] == 1);
+                const bool was_split = !one_pipe && split && ngroups % 2 == 1 && (nsig / ngroups) >= 2;
+                EXPECT(groups == ngroups + (was_split ? 1 : 0));
+                EXPECT((int64_t)plan.size() == (one_pipe ? ngroups : (ngroups + 1) / 2));
+            }
+    EXPECT(mp_batch_plan(0, 8, false, false).empty() && mp_batch_plan(5, 0, false, false).empty());
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <tests/golden> <scratch directory>\n", argv[0]);
@@ -259,6 +297,7 @@ int main(int argc, char** argv) {
     wire_layout();
     tick_rotation();
     batch_plans();
+    mp_batch_plans();
     std::printf("hostonly_driver: %s (%d failed expectation(s))\n", fails ? "FAILED" : "ok", fails);
     return fails ? 1 : 0;
 }
