@@ -1,7 +1,8 @@
 // host/batch_io.hpp -- part of the host side of libcsmp.so (included by csmp.hip, in order; ONE translation unit):
 // the front end of the batch drivers (csmp_omp_batch, csmp_fr_batch, csmp_gomp_batch, csmp_sp_batch, csmp_omp_batch_mfma): the
 // checks they share, B and the outputs of a host caller on the device, the staggered schedule of whole solves on several
-// contexts, and the re-solve of one signal.
+// contexts, the re-solve of one signal, and the two-pipeline scaffold of the omp, fr and mp batches (batch_pipelines: the twin, the
+// solver slots of both contexts, the wide groups' all-or-none slots, the fork and join of the two streams, the drain of a failure).
 // ------------------------------------------------------------------------------------------ batch front end
 // The arguments of one batch call (B: ldB x nsig column-major, idx / val: k x nsig, nnz: nsig) and the device copies a host
 // caller's B and outputs need.  Every temporary is freed on every return path.
@@ -128,6 +129,105 @@ static int batch_stagger(csmp_ctx* const* cc, int T, int64_t nsig, Enqueue&& enq
     const int rc = run();
     if (rc != CSMP_OK)
         for (int w = 0; w < T; ++w) (void)hipStreamSynchronize(cc[w]->stream);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------ two pipelines
+// The scaffold of csmp_omp_batch / csmp_fr_batch (batch_impl, host/forward.hpp) and csmp_mp_batch (host/mp_batch.hpp): a batch on
+// the caller's context and, where wanted, on a twin -- a clone on its own stream -- beside it.
+// Two pipelines: csmp_tune(CSMP_TUNE_PIPELINES, 1) keeps one, 2 and 3 take two whatever the size; automatic where a sweep is long
+// enough for its tail to matter: dictionaries of kPairMinBytes and more (measured: tools/probes/pair_sizes.py)
+static bool batch_two_pipelines(const csmp_ctx* ctx) {
+    constexpr size_t kPairMinBytes = (size_t)4 << 20;  // two pipelines: 1 MiB -10 %, 8 MiB +35 %, 32 MiB +40 %, 64 MiB ... 1 GiB +5 ... +16 %
+    const size_t dict_bytes = (size_t)ctx->Mv * (size_t)ctx->N * (ctx->dtype == CSMP_F32 ? 4 : 8);
+    return ctx->tune_pipelines != 1 && (ctx->tune_pipelines >= 2 || dict_bytes >= kPairMinBytes);
+}
+// the status of a step made on c, the caller's context or its twin: a twin's failure is reported on the caller's context
+static int twin_rc(csmp_ctx* ctx, csmp_ctx* c, int rc) {
+    if (rc != CSMP_OK && c != ctx) ctx->err = c->err;
+    return rc;
+}
+// The solver slots of both contexts made ready, the twin's stream forked behind the caller's, the rounds enqueued, the streams
+// joined.  The slots are q * stride: q < narrow the set the batch cannot run without (slot 0 of the caller's context is the
+// driver's, ready before the call's staging buffers), narrow <= q < wide the wide groups' extension (wide <= narrow: none), with or
+// without a twin.  ensure(c) makes c's active slot ready.  enqueue(tw, granted) enqueues the rounds: tw is the twin or null, granted
+// says whether the extension is there.
+// Device allocations come in this order: the caller's narrow slots, the twin and its narrow slots, then the extension, the caller's
+// before the twin's.  A failure in the extension is not a failure of the call; any other returns its status on the caller's
+// context, both streams drained, the contexts usable.
+template <typename Ensure, typename Enqueue>
+static int batch_pipelines(csmp_ctx* ctx, bool twin, int narrow, int wide, int stride, Ensure&& ensure, Enqueue&& enqueue) {
+    csmp_ctx* tw = nullptr;  // pipeline B's context
+    auto ensure_slots = [&](csmp_ctx* c, int from, int to) -> int {
+        int rc = CSMP_OK;
+        for (int q = from; q < to && rc == CSMP_OK; ++q) {
+            activate_slot(c, q * stride);
+            rc = ensure(c);
+        }
+        activate_slot(c, 0);
+        return twin_rc(ctx, c, rc);
+    };
+    auto run = [&]() -> int {  // (every way out of here passes what follows it below: slot 0 active again on both contexts -- enqueue may
+                               // return with another slot active --, and once the twin exists the drain)
+        CHECK(ensure_slots(ctx, 1, narrow));
+        if (twin) {
+            CHECK(twins_ensure(ctx, 1));
+            tw = ctx->twins[0];
+            tw->prof = ctx->prof;  // (csmp_profile_*: the second pipeline's launches are sampled like the first's)
+            tw->prof_every = ctx->prof_every;
+            CHECK(ensure_slots(tw, 0, narrow));
+        }
+        csmp_ctx* cs[2] = {ctx, tw};
+        bool granted = false;
+        if (wide > narrow) {
+            // the slots beyond the narrow groups': all of them on both contexts, or none -- a device that cannot hold them runs the
+            // groups of sweep_group members it has the slots for (the failure's text, which ensure_slots leaves on the caller's
+            // context, is cleared with the slots)
+            int r3 = CSMP_OK;
+            for (csmp_ctx* c : cs) {
+                if (!c || r3 != CSMP_OK) continue;
+                c->tune_fail_alloc = ctx->tune_fail_alloc;  // (the test hook counts on through the twin's allocations)
+                r3 = ensure_slots(c, narrow, wide);
+                ctx->tune_fail_alloc = c->tune_fail_alloc;
+                if (c != ctx) c->tune_fail_alloc = 0;
+            }
+            granted = r3 == CSMP_OK;
+            if (!granted) {
+                ctx->wide_refused = true;  // (not tried again batch after batch: about a thousand allocations and two drains)
+                for (csmp_ctx* c : cs) {
+                    if (!c) continue;
+                    (void)hipStreamSynchronize(c->stream);
+                    for (int q = narrow; q < wide; ++q) {
+                        activate_slot(c, q * stride);
+                        solver_free(c->s);
+                    }
+                    activate_slot(c, 0);
+                    c->err.clear();
+                }
+                (void)hipGetLastError();
+            }
+        }
+        if (tw) {
+            if (!ctx->ev_twin) HIPCHECK(hipEventCreateWithFlags(&ctx->ev_twin, hipEventDisableTiming));
+            if (!tw->ev_twin) HIPCHECK(hipEventCreateWithFlags(&tw->ev_twin, hipEventDisableTiming));
+            // (the twin starts behind everything this context's stream holds: the caller's buffers, the slots' allocation)
+            HIPCHECK(hipEventRecord(ctx->ev_twin, ctx->stream));
+            HIPCHECK(hipStreamWaitEvent(tw->stream, ctx->ev_twin, 0));
+        }
+        CHECK(enqueue(tw, granted));
+        if (tw) {  // this context's stream goes on behind the twin's last launch
+            HIPCHECK(hipEventRecord(tw->ev_twin, tw->stream));
+            HIPCHECK(hipStreamWaitEvent(ctx->stream, tw->ev_twin, 0));
+        }
+        return CSMP_OK;
+    };
+    const int rc = run();
+    activate_slot(ctx, 0);
+    if (tw) activate_slot(tw, 0);
+    if (rc != CSMP_OK && tw) {  // (a failed enqueue: both streams drained before anything is released)
+        (void)hipStreamSynchronize(tw->stream);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
     return rc;
 }
 

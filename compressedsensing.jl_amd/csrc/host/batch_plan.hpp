@@ -41,10 +41,23 @@ struct PlanRound {
     PlanGroup g[2][3];  // [pipeline: 0 = A, the caller's context; 1 = B, the twin][group]; member m of group g is solver slot g + 3 m
 };
 
+// The fewest shared passes for nsig signals, R to a pass at the most: ceil(nsig / R) groups of consecutive signals, their sizes as
+// even as possible, the larger ones first
+static std::vector<PlanGroup> even_groups(int64_t nsig, int R) {
+    std::vector<PlanGroup> groups;
+    if (nsig < 1 || R < 1) return groups;
+    const int64_t ngroups = (nsig + R - 1) / R, base = nsig / ngroups, extra = nsig % ngroups;
+    int64_t at = 0;
+    for (int64_t i = 0; i < ngroups; ++i) {
+        groups.push_back({at, (int)(base + (i < extra ? 1 : 0))});
+        at += groups.back().size;
+    }
+    return groups;
+}
+
 // The rounds of a batch of nsig signals (R: the members a shared pass serves, ctx->sweep_group or ctx->group_wide).  Pairs: rounds of 3 + 3 while six or
-// more signals remain, then 1 + 1, then a lone signal in the one-pipeline form.  Grouped: the fewest shared passes -- ceil(nsig / R)
-// groups of consecutive signals, their sizes as even as possible -- dealt six to a round, even offsets to A and odd ones to B; a last
-// round may leave B with no group and keeps the pair form.
+// more signals remain, then 1 + 1, then a lone signal in the one-pipeline form.  Grouped: the fewest shared passes (even_groups)
+// dealt six to a round, even offsets to A and odd ones to B; a last round may leave B with no group and keeps the pair form.
 static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int R, bool one_pipe = false) {
     std::vector<PlanRound> rounds;
     auto round = [&](RoundForm form) -> PlanRound& {
@@ -81,15 +94,12 @@ static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int 
             if (at < nsig) round(RoundForm::One).g[0][0] = {at, 1};
             break;
         case BatchSchedule::Grouped: {
-            if (nsig < 1 || R < 1) break;
-            const int64_t ngroups = (nsig + R - 1) / R, base = nsig / ngroups, extra = nsig % ngroups;
-            for (int64_t i = 0; i < ngroups; ++i) {
-                const int per = one_pipe ? 3 : 6;  // (one_pipe, a measurement: three groups to a round, all on A; B stays empty)
+            const std::vector<PlanGroup> groups = even_groups(nsig, R);
+            for (size_t i = 0; i < groups.size(); ++i) {
+                const size_t per = one_pipe ? 3 : 6;  // (one_pipe, a measurement: three groups to a round, all on A; B stays empty)
                 if (i % per == 0) round(RoundForm::Grouped);
-                const int size = (int)(base + (i < extra ? 1 : 0));
-                if (one_pipe) rounds.back().g[0][i % 3] = {at, size};
-                else rounds.back().g[i % 2][(i % 6) / 2] = {at, size};
-                at += size;
+                if (one_pipe) rounds.back().g[0][i % 3] = groups[i];
+                else rounds.back().g[i % 2][(i % 6) / 2] = groups[i];
             }
             break;
         }
@@ -98,8 +108,8 @@ static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int 
 }
 
 // The rounds of csmp_mp_batch (host/mp_batch.hpp): a round is ONE group per pipeline -- MP has no append stages to rotate, a step of
-// a group is its shared pass and one short launch --, up to 2 R signals (R: the members a pass serves).  The fewest passes:
-// ceil(nsig / R) groups of consecutive signals, their sizes as even as possible, dealt two to a round, A then B.  one_pipe: every
+// a group is its shared pass and one short launch --, up to 2 R signals (R: the members a pass serves).  The fewest passes
+// (even_groups), dealt two to a round, A then B.  one_pipe: every
 // round holds one group, on A.  split_lone: a round that would hold a single group of two or more signals on A -- a batch of up to R
 // signals, the last round of an odd number of groups -- is cut into two halves, A's the larger, so that each half's short launch
 // falls under the other's pass (one pass more; kMpSplitLone, host/mp_batch.hpp, says which was faster).
@@ -108,20 +118,17 @@ struct MpRound {
 };
 static std::vector<MpRound> mp_batch_plan(int64_t nsig, int R, bool one_pipe, bool split_lone) {
     std::vector<MpRound> rounds;
-    if (nsig < 1 || R < 1) return rounds;
-    const int64_t ngroups = (nsig + R - 1) / R, base = nsig / ngroups, extra = nsig % ngroups;
-    int64_t at = 0;
-    for (int64_t i = 0; i < ngroups; ++i) {
-        const int size = (int)(base + (i < extra ? 1 : 0));
+    const std::vector<PlanGroup> groups = even_groups(nsig, R);
+    for (size_t i = 0; i < groups.size(); ++i) {
+        const PlanGroup& g = groups[i];
         if (one_pipe || i % 2 == 0) rounds.emplace_back();
         MpRound& r = rounds.back();
-        if (!one_pipe && split_lone && i % 2 == 0 && i + 1 == ngroups && size >= 2) {
-            r.g[0] = {at, (size + 1) / 2};
-            r.g[1] = {at + (size + 1) / 2, size / 2};
+        if (!one_pipe && split_lone && i % 2 == 0 && i + 1 == groups.size() && g.size >= 2) {
+            r.g[0] = {g.first, (g.size + 1) / 2};
+            r.g[1] = {g.first + (g.size + 1) / 2, g.size / 2};
         } else {
-            r.g[one_pipe ? 0 : i % 2] = {at, size};
+            r.g[one_pipe ? 0 : i % 2] = g;
         }
-        at += size;
     }
     return rounds;
 }

@@ -217,7 +217,7 @@ struct csmp_ctx {
     double scr_cert_abs = 0.0, scr_cert_rel = 0.0, scr_cert_abs2 = 0.0;
     int scr_kwin = 0;
     int scr_image = 1;       // the image the screened sweeps of this context read: 1 bf16, 2 int8 (option 2 on a flat dictionary)
-    bool scr_lone = false;   // the solve in progress runs alone on the GPU (csmp_omp, csmp_mp): the pick kernel may take a whole CU
+    bool scr_lone = false;   // the solve in progress runs alone on the GPU (LoneGuard, below): the pick kernel may take a whole CU
     int opt_screened = 0;         // CSMP_OPT_SCREENED_SWEEP: csmp_omp / csmp_omp_batch / csmp_gomp sweep the bf16 image and certify (csmp_screened.hpp)
     int opt_batch_screen = 3;     // CSMP_OPT_BATCH_SCREEN: 3 (default) binary16 operands, 0 bf16, 1 int8, 2 int8 where the dictionary is flat (int8: statistical certificate only)
     size_t sweep_lds = 0;
@@ -250,6 +250,15 @@ struct csmp_ctx {
     size_t ev2_used = 0;
     int64_t prof2_n = 0;
     double prof2_ms = 0.0;
+};
+// scr_lone for the length of a solve that runs alone on the GPU (csmp_omp, csmp_mp, csmp_gomp, csmp_ompr, a lone signal of
+// csmp_mp_batch): set here, reset on every way out of the scope
+struct LoneGuard {
+    csmp_ctx* c;
+    explicit LoneGuard(csmp_ctx* x) : c(x) { c->scr_lone = true; }
+    ~LoneGuard() { c->scr_lone = false; }
+    LoneGuard(const LoneGuard&) = delete;
+    LoneGuard& operator=(const LoneGuard&) = delete;
 };
 
 #define HIPCHECK(expr)                                                                          \

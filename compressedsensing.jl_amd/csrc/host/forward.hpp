@@ -1,5 +1,6 @@
 // host/forward.hpp -- part of the host side of libcsmp.so (included by csmp.hip, in order; ONE translation unit):
-// forward regression (OLS) sweeps and drivers; the omp / fr batch drivers; mp.
+// forward regression (OLS) sweeps and drivers; the omp / fr batch drivers (batch_impl: the schedule, the rounds and the re-solves, on
+// the two-pipeline scaffold of host/batch_io.hpp); mp (mp_solve: the one MP solve csmp_mp and csmp_mp_batch's lone signals share).
 // ------------------------------------------------------------------------------------------ forward regression (OLS)
 // one pass of k_fr_sweep (csmp_forward.hpp): nq = -1 first step (norms), 0 scores only, 1 / 2 directions
 struct FrPass {
@@ -257,15 +258,11 @@ static BatchSchedule batch_schedule(const csmp_ctx* ctx, bool isfr, int64_t nsig
     // share the HBM, out of step with one another: the last workgroups of one tick, its launch boundary and the staging of its
     // residual image fall under the other pipeline's stream instead of leaving the memory system idle (DESIGN.md section 0, round 6:
     // 6.03e3 -> 6.46e3 atoms/s with 192 sweep workgroups each).
-    // From two signals on and dictionaries of 4 MiB on; csmp_tune(CSMP_TUNE_PIPELINES, 1) keeps one, 2 takes two whatever the size.
+    // From two signals on and where batch_two_pipelines (host/batch_io.hpp) says so: by size, or as csmp_tune(CSMP_TUNE_PIPELINES) asks.
     // (forward regression too: its ticks under the same LDS request -- one workgroup per CU -- 6.28e3 -> 6.57e3 atoms/s at the benchmark
     // shape; without the request 6.47e3.  With the sweep body as round 5 left it the same pairing had measured 5.99e3 against 5.96e3.)
-    // ... and where a sweep is long enough for its tail to matter: dictionaries of kPairMinBytes and more (measured: tools/probes/
-    // pair_sizes.py)
     constexpr int64_t kPairMinSignals = 2;
-    constexpr size_t kPairMinBytes = (size_t)4 << 20;  // two pipelines: 1 MiB -10 %, 8 MiB +35 %, 32 MiB +40 %, 64 MiB ... 1 GiB +5 ... +16 %
-    const size_t dict_bytes = (size_t)ctx->Mv * (size_t)ctx->N * (ctx->dtype == CSMP_F32 ? 4 : 8);
-    if (nsig < kPairMinSignals || ctx->tune_pipelines == 1 || (ctx->tune_pipelines < 2 && dict_bytes < kPairMinBytes)) return BatchSchedule::One;
+    if (nsig < kPairMinSignals || !batch_two_pipelines(ctx)) return BatchSchedule::One;
     // GROUPED (omp only): each pipeline's three slots become three groups of up to sweep_group signals whose sweeps share one pass over
     // A (group_pipe_launch).  csmp_tune(CSMP_TUNE_PIPELINES, 3) forces it; automatic wherever two pipelines run and a pass serves two or
     // more signals.  Supports beyond qr_max_cols(), screened sweeps (csmp_omp_batch) and fr keep the schedules above.
@@ -355,104 +352,38 @@ static int batch_impl(csmp_ctx* ctx, BatchIO& io, bool isfr, double eps, double 
     const bool twin = sched == BatchSchedule::Pairs || sched == BatchSchedule::Grouped;
     const int nslots = sched == BatchSchedule::Grouped ? 3 * ctx->sweep_group : 3;
     // wide groups: passes of up to group_wide members where the batch has more signals than a narrow pass serves, on 3 * group_wide slots
-    int members = ctx->sweep_group;
     const int nslots_wide = sched == BatchSchedule::Grouped && ctx->group_wide > ctx->sweep_group && nsig > ctx->sweep_group && !ctx->wide_refused ? 3 * ctx->group_wide : 0;
-    csmp_ctx* tw = nullptr;  // pipeline B's context: a clone of this one on its own stream
-    auto ensure_slots = [&](csmp_ctx* c, int from, int to) -> int {
-        int r2 = CSMP_OK;
-        for (int q = from; q < to && r2 == CSMP_OK; ++q) {
-            activate_slot(c, q);
-            r2 = solver_ensure(c, kc, (int)k);
-            if (r2 == CSMP_OK && isfr) r2 = fr_ensure(c);
-        }
-        activate_slot(c, 0);
-        return r2;
+    auto ensure = [&](csmp_ctx* c) -> int {  // c's active slot ready for a chain of this batch
+        CHECK(solver_ensure(c, kc, (int)k));
+        return isfr ? fr_ensure(c) : CSMP_OK;
     };
-    // f(context, signal) for every member of a round with its slot active: A's groups, then B's, group by group, member by member
-    auto each_member = [&](const PlanRound& r, auto&& f) -> int {
-        csmp_ctx* cs[2] = {ctx, tw};
-        for (int p = 0; p < 2; ++p)
-            for (int g = 0; g < 3; ++g)
-                for (int m = 0; m < r.g[p][g].size; ++m) {
-                    activate_slot(cs[p], g + 3 * m);
-                    const int r2 = f(cs[p], r.g[p][g].first + m);
-                    if (r2 != CSMP_OK) {
-                        if (cs[p] != ctx) ctx->err = cs[p]->err;
-                        return r2;
+    auto run_plan = [&](csmp_ctx* tw, bool wide) -> int {
+        // f(context, signal) for every member of a round with its slot active: A's groups, then B's, group by group, member by member
+        auto each_member = [&](const PlanRound& r, auto&& f) -> int {
+            csmp_ctx* cs[2] = {ctx, tw};
+            for (int p = 0; p < 2; ++p)
+                for (int g = 0; g < 3; ++g)
+                    for (int m = 0; m < r.g[p][g].size; ++m) {
+                        activate_slot(cs[p], g + 3 * m);
+                        CHECK(twin_rc(ctx, cs[p], f(cs[p], r.g[p][g].first + m)));
                     }
-                }
-        return CSMP_OK;
-    };
-    auto run_plan = [&]() -> int {  // (every way out of here once the twin exists passes the drain below)
-        CHECK(ensure_slots(ctx, 1, nslots));
-        if (twin) {
-            CHECK(twins_ensure(ctx, 1));
-            tw = ctx->twins[0];
-            tw->prof = ctx->prof;  // (csmp_profile_*: the second pipeline's launches are sampled like the first's)
-            tw->prof_every = ctx->prof_every;
-            const int r2 = ensure_slots(tw, 0, nslots);
-            if (r2 != CSMP_OK) {
-                ctx->err = tw->err;
-                return r2;
-            }
-            if (nslots_wide > 0) {
-                // the slots beyond the narrow groups': all of them on both contexts, or none -- a device that cannot hold them runs
-                // the groups of sweep_group members it has the slots for
-                csmp_ctx* cs[2] = {ctx, tw};
-                int r3 = CSMP_OK;
-                for (csmp_ctx* c : cs) {
-                    if (r3 != CSMP_OK) break;
-                    c->tune_fail_alloc = ctx->tune_fail_alloc;  // (the test hook counts on through the twin's allocations)
-                    r3 = ensure_slots(c, nslots, nslots_wide);
-                    ctx->tune_fail_alloc = c->tune_fail_alloc;
-                    if (c != ctx) c->tune_fail_alloc = 0;
-                }
-                if (r3 == CSMP_OK) {
-                    members = ctx->group_wide;
-                } else {
-                    ctx->wide_refused = true;  // (not tried again batch after batch: about a thousand allocations and two drains)
-                    for (csmp_ctx* c : cs) {
-                        (void)hipStreamSynchronize(c->stream);
-                        for (int q = nslots; q < nslots_wide; ++q) {
-                            activate_slot(c, q);
-                            solver_free(c->s);
-                        }
-                        activate_slot(c, 0);
-                        c->err.clear();
-                    }
-                    (void)hipGetLastError();
-                }
-            }
-            if (!ctx->ev_twin) HIPCHECK(hipEventCreateWithFlags(&ctx->ev_twin, hipEventDisableTiming));
-            if (!tw->ev_twin) HIPCHECK(hipEventCreateWithFlags(&tw->ev_twin, hipEventDisableTiming));
-            // (the twin starts behind everything this context's stream holds: the caller's buffers, the slots' allocation)
-            HIPCHECK(hipEventRecord(ctx->ev_twin, ctx->stream));
-            HIPCHECK(hipStreamWaitEvent(tw->stream, ctx->ev_twin, 0));
-        }
+            return CSMP_OK;
+        };
         // Wide groups keep the plan's dealing over both pipelines (18 signals: groups 0 and 2 on A, 1 on B).  Measured on the benchmark,
         // atoms/s at 18 / 20 signals, two runs each: 2 + 1 on 256 workgroups 26 087, 26 176 / 27 622, 27 735; three groups on ONE pipeline
         // (csmp_tune group_wide 2) 25 257, 25 071 / 26 958, 27 060 -- its append launches have no other pipeline's sweep to run under.
-        for (const PlanRound& r : batch_plan(nsig, sched, members, members > ctx->sweep_group && ctx->tune_group_wide == 2)) {
+        const int members = wide ? ctx->group_wide : ctx->sweep_group;
+        for (const PlanRound& r : batch_plan(nsig, sched, members, wide && ctx->tune_group_wide == 2)) {
             CHECK(each_member(r, init));
             CHECK(ctx->dtype == CSMP_F32 ? run_round<float>(r, ctx, tw, isfr, k, eps, p2) : run_round<double>(r, ctx, tw, isfr, k, eps, p2));
             CHECK(each_member(r, finish));
-        }
-        if (twin) {  // this context's stream goes on behind the twin's last launch
-            HIPCHECK(hipEventRecord(tw->ev_twin, tw->stream));
-            HIPCHECK(hipStreamWaitEvent(ctx->stream, tw->ev_twin, 0));
         }
         return CSMP_OK;
     };
     if (sched == BatchSchedule::Signals) {
         for (int64_t sgn = 0; sgn < nsig && rc == CSMP_OK; ++sgn) rc = solve_one(sgn, true);
     } else {
-        rc = run_plan();
-        activate_slot(ctx, 0);
-        if (tw) activate_slot(tw, 0);
-        if (rc != CSMP_OK && tw) {  // (a failed enqueue: both streams drained before anything is released)
-            (void)hipStreamSynchronize(tw->stream);
-            (void)hipStreamSynchronize(ctx->stream);
-        }
+        rc = batch_pipelines(ctx, twin, nslots, nslots_wide, 1, ensure, run_plan);
     }
     // ... then ONE synchronisation: a signal whose support failed the DGKS test (flagged on the
     // device, nothing committed for the failing column) is solved again with the full chain
@@ -549,26 +480,18 @@ static int mp_step(csmp_ctx* ctx) {
     return launch_mp_update(ctx);
 }
 
-extern "C" int csmp_mp(csmp_ctx* ctx, const void* b, int b_dtype, int64_t k, const int64_t* idx0, const double* val0,
-                       int64_t nnz0, int64_t* idx, double* val, int64_t* nnz) {
-    if (!ctx) return CSMP_EINVAL;
-    if (!b || k < 0 || nnz0 < 0 || (nnz0 > 0 && (!idx0 || !val0))) return fail(ctx, CSMP_EINVAL, "mp: bad arguments");
-    if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
-    HIPCHECK(hipSetDevice(ctx->dev));
-    CHECK(solver_ensure(ctx, (int)std::max<int64_t>(std::max(k, nnz0), 1), 1, false));  // MP keeps no factorisation
-    ctx->s.begun = false;
-    // CSMP_OPT_SCREENED_SWEEP: the sweeps read the image, every pick is certified (host/screened.hpp); a solve with an uncertified
-    // pick is repeated with the exact sweep
+// One MP solve of k steps on the active slot.  load() puts the signal there (and a warm start's support); it runs again before a
+// repeat.  CSMP_OPT_SCREENED_SWEEP: the sweeps read the image, every pick is certified (host/screened.hpp); a solve with an
+// uncertified pick is repeated with the exact sweep.  The log of (atom, coefficient) pairs stays on the device: csmp_mp reads it
+// with mp_collect, csmp_mp_batch's lone signals with mp_emit (host/mp_batch.hpp).  scr_lone is set for the steps only: it is reset
+// before the caller's output step, which launches no pick kernel.
+template <typename Load>
+static int mp_solve(csmp_ctx* ctx, int64_t k, Load&& load) {
     bool screened = screened_on(ctx);
     if (screened) CHECK(screened_ensure(ctx));
-    ctx->scr_lone = true;  // (one solve at a time: reset on every way out below)
-    struct LoneReset {
-        csmp_ctx* c;
-        ~LoneReset() { c->scr_lone = false; }
-    } lone_reset{ctx};
+    LoneGuard lone_guard(ctx);  // (one solve at a time)
     for (int attempt = 0; attempt < 2; ++attempt) {
-        CHECK(upload_b(ctx, b, b_dtype));
-        if (nnz0 > 0) CHECK(upload_support(ctx, idx0, val0, nnz0));
+        CHECK(load());
         for (int64_t t = 0; t < k; ++t) {
             if (screened) {
                 Solver& s = ctx->s;
@@ -588,5 +511,20 @@ extern "C" int csmp_mp(csmp_ctx* ctx, const void* b, int b_dtype, int64_t k, con
         ctx->scr_fallbacks += 1;
         screened = false;
     }
+    return CSMP_OK;
+}
+
+extern "C" int csmp_mp(csmp_ctx* ctx, const void* b, int b_dtype, int64_t k, const int64_t* idx0, const double* val0,
+                       int64_t nnz0, int64_t* idx, double* val, int64_t* nnz) {
+    if (!ctx) return CSMP_EINVAL;
+    if (!b || k < 0 || nnz0 < 0 || (nnz0 > 0 && (!idx0 || !val0))) return fail(ctx, CSMP_EINVAL, "mp: bad arguments");
+    if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
+    HIPCHECK(hipSetDevice(ctx->dev));
+    CHECK(solver_ensure(ctx, (int)std::max<int64_t>(std::max(k, nnz0), 1), 1, false));  // MP keeps no factorisation
+    ctx->s.begun = false;
+    CHECK(mp_solve(ctx, k, [&]() -> int {
+        CHECK(upload_b(ctx, b, b_dtype));
+        return nnz0 > 0 ? upload_support(ctx, idx0, val0, nnz0) : CSMP_OK;
+    }));
     return mp_collect(ctx, idx0, val0, nnz0, idx, val, nnz);
 }

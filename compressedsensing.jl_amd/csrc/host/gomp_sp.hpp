@@ -128,11 +128,7 @@ extern "C" int csmp_gomp(csmp_ctx* ctx, const void* b, int b_dtype, int64_t l, i
     // with an uncertified step is repeated with the exact sweep.
     bool screened = screened_on(ctx) && l <= kTopSmall;
     if (screened) CHECK(screened_ensure(ctx));
-    ctx->scr_lone = true;  // (one solve at a time: the pick kernel may take a whole CU)
-    struct LoneReset {
-        csmp_ctx* c;
-        ~LoneReset() { c->scr_lone = false; }
-    } lone_reset{ctx};
+    LoneGuard lone_guard(ctx);  // (one solve at a time: the pick kernel may take a whole CU)
     bool block = l <= kPanelMax;
     for (int attempt = 0; attempt < 4; ++attempt) {
         CHECK(upload_b(ctx, b, b_dtype));

@@ -1,5 +1,6 @@
 // host/omp.hpp -- part of the host side of libcsmp.so (included by csmp.hip, in order; ONE translation unit):
-// the tick pipeline (three signals in flight) and the omp driver.
+// the tick pipeline (three signals in flight), the grouped scheduler with the shared pass of a group (shared_pass_launch: csmp_mp_batch
+// launches it too) and the omp driver.
 // ------------------------------------------------------------------------------------------ tick kernel (3 signals in flight)
 template <typename TA>
 static TickSweep<TA> tick_sweep_params(csmp_ctx* ctx, Solver& s, double eps, int check_eps, int skipmask, int nblk, int active) {
@@ -229,6 +230,26 @@ static hipError_t multi_launch(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t ld
     }
     return multi_launch_u<TA, 4>(ctx, p, lds);
 }
+// The shared pass of a group: the `size` members in the slots slot0, slot0 + 3, ... sweep in ONE launch that reads A once for all of
+// them -- the narrow pass on nblk workgroups, for more than kGroupMax members (more than a workgroup has images) the wide pass on
+// nblk_wide, two workgroups per read of A -- under an LDS request of at least lds_sweep.  group_pipe_launch's sweep stage and a
+// step of csmp_mp_batch's groups (mp_group_step, host/mp_batch.hpp).
+template <typename TA>
+static int shared_pass_launch(csmp_ctx* ctx, int slot0, int size, double eps, int check_eps, int skipmask, int nblk, int nblk_wide,
+                              size_t lds_sweep) {
+    MultiSweep<TA> p;
+    p.A = (const TA*)ctx->dA; p.ld = ctx->ld; p.Mv = ctx->Mv; p.N = ctx->N;
+    const bool wide = size > kGroupMax;
+    p.eps = eps; p.check_eps = check_eps; p.skipmask = skipmask; p.nblk = wide ? nblk_wide : nblk; p.KP = ctx->sweep_KP;
+    multi_members<TA>(ctx, p, slot0, size);
+    // ONE sampled launch per shared pass: it reads A once, whatever the group size
+    const bool timed = prof_pick(ctx);
+    if (timed) CHECK(prof_mark(ctx));
+    const size_t lds = std::max(sweep_multi_lds_bytes(p.KP, p.n), lds_sweep);
+    HIPCHECK(wide ? wide_launch<TA>(ctx, p, lds) : multi_launch<TA>(ctx, p, lds));
+    if (timed) CHECK(prof_mark(ctx));
+    return CSMP_OK;
+}
 template <typename TA>
 static int group_pipe_launch(Pipe& gp, int64_t n) {
     csmp_ctx* ctx = gp.ctx;
@@ -253,19 +274,7 @@ static int group_pipe_launch(Pipe& gp, int64_t n) {
         hipLaunchKernelGGL(kern, dim3((a.n1 + a.n2) * G), dim3(kSweepThreads), gp.lds, ctx->stream, a, G);
         HIPCHECK(hipGetLastError());
     }
-    if (t.az) {
-        MultiSweep<TA> p;
-        p.A = (const TA*)ctx->dA; p.ld = ctx->ld; p.Mv = ctx->Mv; p.N = ctx->N;
-        const bool wide = gp.size[t.z] > kGroupMax;  // (more members than a workgroup has images: two workgroups per read of A)
-        p.eps = gp.eps; p.check_eps = t.tz > 0 ? 1 : 0; p.skipmask = skip; p.nblk = wide ? gp.nblk_wide : gp.nblk; p.KP = ctx->sweep_KP;
-        multi_members<TA>(ctx, p, t.z, gp.size[t.z]);
-        // ONE sampled launch per shared pass: it reads A once, whatever the group size
-        const bool timed = prof_pick(ctx);
-        if (timed) CHECK(prof_mark(ctx));
-        const size_t lds = std::max(sweep_multi_lds_bytes(p.KP, p.n), gp.lds_sweep);
-        HIPCHECK(wide ? wide_launch<TA>(ctx, p, lds) : multi_launch<TA>(ctx, p, lds));
-        if (timed) CHECK(prof_mark(ctx));
-    }
+    if (t.az) CHECK(shared_pass_launch<TA>(ctx, t.z, gp.size[t.z], gp.eps, t.tz > 0 ? 1 : 0, skip, gp.nblk, gp.nblk_wide, gp.lds_sweep));
     return CSMP_OK;
 }
 
@@ -275,12 +284,7 @@ template <int (*launch)(Pipe&, int64_t)>
 static int pipe_ticks(Pipe& a, Pipe* b) {
     for (int64_t n = 0; n < 3 * a.k + 2; ++n) {
         CHECK(launch(a, n));
-        if (!b) continue;
-        const int rc = launch(*b, n);
-        if (rc != CSMP_OK) {
-            a.ctx->err = b->ctx->err;
-            return rc;
-        }
+        if (b) CHECK(twin_rc(a.ctx, b->ctx, launch(*b, n)));
     }
     return CSMP_OK;
 }
@@ -302,11 +306,7 @@ extern "C" int csmp_omp(csmp_ctx* ctx, const void* b, int b_dtype, int64_t k, do
     // device, nothing committed) the solve is repeated with the second Gram-Schmidt pass enabled
     bool screened = screened_on(ctx);
     if (screened) CHECK(screened_ensure(ctx));
-    struct LoneGuard {  // (csmp_omp is one solve at a time)
-        csmp_ctx* c;
-        explicit LoneGuard(csmp_ctx* x) : c(x) { c->scr_lone = true; }
-        ~LoneGuard() { c->scr_lone = false; }
-    } lone_guard(ctx);
+    LoneGuard lone_guard(ctx);  // (csmp_omp is one solve at a time)
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool uncertain = false;
         for (int pass = 0; pass < 2; ++pass) {

@@ -382,11 +382,7 @@ extern "C" int csmp_ompr(csmp_ctx* ctx, const void* b, int b_dtype, int64_t k, d
     HIPCHECK(hipSetDevice(ctx->dev));
     OmprJob& j = ompr_job(ctx);
     CHECK(j.begin(ctx, b, b_dtype, k));
-    ctx->scr_lone = true;
-    struct LoneReset {
-        csmp_ctx* c;
-        ~LoneReset() { c->scr_lone = false; }
-    } lone_reset{ctx};
+    LoneGuard lone_guard(ctx);
     CHECK(j.acquire());
     int64_t it = 0;
     while (it < maxiter) {  // :193
