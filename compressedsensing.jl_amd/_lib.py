@@ -81,6 +81,7 @@ SIGNATURES = {
     "csmp_solver_acquire": (C.c_int, [vp, i64]),
     "csmp_solver_remove": (C.c_int, [vp, i64]),
     "csmp_solver_state": (C.c_int, [vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp, C.POINTER(C.c_int)]),
+    "csmp_ista": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, i64, i64, C.c_double, C.c_int, vp, C.c_int, C.POINTER(C.c_double)]),
     "csmp_sweep": (C.c_int, [vp, vp, vp, i64, vp, vp]),
     "csmp_lstsq": (C.c_int, [vp, vp, i64, vp, C.c_int, vp]),
 }
@@ -630,6 +631,41 @@ class Context:
     def shard_append(self, recs, nrec):
         assert recs.is_cuda and recs.is_contiguous() and recs.numel() * recs.element_size() >= nrec * self.shard_record_bytes()
         self.call("csmp_shard_append", vp(recs.data_ptr()), int(nrec))
+
+    # ---- l1-regularised least squares
+    def _ista_args(self, w, idx0, val0):
+        w = np.ascontiguousarray(np.atleast_1d(w), dtype=np.float64)
+        if w.ndim != 1:
+            raise CsmpError(EDIM, "the weights must be a scalar or a vector")
+        idx0 = np.zeros(0, np.int64) if idx0 is None else np.ascontiguousarray(idx0, dtype=np.int64)
+        val0 = np.zeros(0, np.float64) if val0 is None else np.ascontiguousarray(val0, dtype=np.float64)
+        if idx0.shape != val0.shape or idx0.ndim != 1:
+            raise CsmpError(EDIM, "warm start: idx0 and val0 must be vectors of one length")
+        return w, idx0, val0
+
+    def ista(self, b, w, idx0=None, val0=None, maxiter=1024, stepsize=1e-2, accel=False):
+        """csmp_ista on a host signal: (dense x, Float64[N]; ||b - A x||).  w: one weight or N of them; idx0 / val0: the warm start."""
+        b = self._b(b)
+        w, idx0, val0 = self._ista_args(w, idx0, val0)
+        x = np.zeros(self.N, np.float64)
+        rn = C.c_double(0)
+        self.call("csmp_ista", ptr(b), dtype_code(b.dtype), ptr(w), i64(len(w)), ptr(idx0), ptr(val0), i64(len(idx0)), i64(int(maxiter)),
+                  C.c_double(stepsize), int(bool(accel)), ptr(x), HOST, C.byref(rn))
+        return x, rn.value
+
+    def ista_device(self, b, w, x, idx0=None, val0=None, maxiter=1024, stepsize=1e-2, accel=False):
+        """torch CUDA tensors: b (M,) float32 / float64, x (N,) float64 receives the dense result.  Returns ||b - A x||; the work is done
+        when the call returns."""
+        import torch
+        if not (b.is_cuda and b.is_contiguous() and b.shape == (self.M,) and b.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "b must be a contiguous CUDA vector of length size(A, 1), float32 or float64")
+        if not (x.is_cuda and x.is_contiguous() and x.shape == (self.N,) and x.dtype == torch.float64):
+            raise CsmpError(EDIM, "x must be a contiguous CUDA float64 vector of length size(A, 2)")
+        w, idx0, val0 = self._ista_args(w, idx0, val0)
+        rn = C.c_double(0)
+        self.call("csmp_ista", vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64, ptr(w), i64(len(w)), ptr(idx0), ptr(val0),
+                  i64(len(idx0)), i64(int(maxiter)), C.c_double(stepsize), int(bool(accel)), vp(x.data_ptr()), DEVICE, C.byref(rn))
+        return rn.value
 
     # ---- primitives
     def sweep(self, r, topk=1, want_abs=True):

@@ -15,6 +15,7 @@ Same names, argument meaning and error behaviour as the reference (paths relativ
     ompr(A, b, k, delta; maxiter)            src/twostage.jl:184-202
     MP / OMP / GOMP functors with update!    src/matchingpursuit.jl:10-31,44-70,95-123
     argmaxinner!(P[, k])                     src/matchingpursuit.jl:181-193
+    ista(A, b, λ | w[, x]; maxiter, stepsize) / fista(...) / shrinkage(x, α)   src/basispursuit.jl:144,164-204
 
 `A` is either a numpy matrix (uploaded to HBM for the duration of the call) or a `Dictionary`
 (uploaded once, resident -- what a caller looping over many signals wants).  Results are
@@ -142,6 +143,45 @@ def mp(A, b, k, x=None):
     finally:
         if tmp:
             D.close()
+
+
+def shrinkage(x, a):
+    """shrinkage(x, α) = sign(x) max(|x| - α, 0), the soft-thresholding operator (src/basispursuit.jl:144); scalars or arrays."""
+    return np.sign(x) * np.maximum(np.abs(x) - a, 0.0)
+
+
+def _ista(A, b, lam_or_w, x, maxiter, stepsize, accel):
+    M, N, _ = _meta(A)
+    w = np.atleast_1d(np.asarray(lam_or_w, dtype=np.float64))
+    if w.ndim != 1 or len(w) not in (1, N):
+        raise ValueError(f"length(w) = {w.shape} but size(A, 2) = {N}")  # DimensionMismatch("length(x) ≠ length(w)"), :155
+    if not maxiter >= 0:
+        raise ValueError(f"maxiter = {maxiter} has to be non-negative")
+    if not (stepsize > 0 and np.isfinite(stepsize)):
+        raise ValueError(f"stepsize = {stepsize} has to be positive and finite")
+    D, tmp = _dict(A)
+    try:
+        i0 = v0 = None
+        if x is not None and x.nnz:
+            i0, v0 = x.nzind, x.nzval
+        xd, _ = D.ctx.ista(b, w, i0, v0, maxiter=int(maxiter), stepsize=float(stepsize), accel=accel)
+        nz = np.flatnonzero(xd)  # dropzeros!: an exact zero is a structural zero (:180)
+        return SparseVector(N, nz, xd[nz])
+    finally:
+        if tmp:
+            D.close()
+
+
+def ista(A, b, lam_or_w, x=None, *, maxiter=1024, stepsize=1e-2):
+    """ista(A,b,λ,x=spzeros(N); maxiter=1024, stepsize=1e-2) | ista(A,b,w,x; ...): exactly maxiter steps of
+    x <- shrinkage(x + 2α A'(b - A x), wα) on ‖b - A x‖² + Σ w_j |x_j| (src/basispursuit.jl:164-183).  x is a warm start (not changed)."""
+    return _ista(A, b, lam_or_w, x, maxiter, stepsize, False)
+
+
+def fista(A, b, lam_or_w, x=None, *, maxiter=1024, stepsize=1e-2):
+    """fista(A,b,λ | w,x; maxiter, stepsize): Beck-Teboulle acceleration of ista on the same objective -- t₁ = 1,
+    t⁺ = (1 + √(1 + 4t²))/2, y⁺ = x⁺ + ((t - 1)/t⁺)(x⁺ - x).  The reference's own fista (:186-204) does not run."""
+    return _ista(A, b, lam_or_w, x, maxiter, stepsize, True)
 
 
 def sp(A, b, k, delta=1e-12, maxiter=None):

@@ -16,6 +16,7 @@
 #include "csmp_shard.hpp"
 #include "csmp_gram.hpp"
 #include "csmp_swap.hpp"
+#include "csmp_ista.hpp"
 
 #include <algorithm>
 #include <iterator>
@@ -50,5 +51,6 @@ using namespace csmp;
 #include "host/steps_twostage.hpp"
 #include "host/batched.hpp"
 #include "host/screened.hpp"
+#include "host/ista.hpp"
 #include "host/measure.hpp"
 #include "host/rccl.hpp"

@@ -133,6 +133,16 @@ struct DictShare {
     int kind = 0;  // how p is given back: 0 hipFree (HBM), 1 hipHostFree (library-owned page-locked memory), 2 hipHostUnregister (the caller's)
 };
 
+// ista / fista (csmp_ista.hpp, host/ista.hpp): the iterates, the list of the next y's non-zeros and the axpy's partials, made on
+// first use, sized by the dictionary
+struct IstaBuf {
+    double *x = nullptr, *y = nullptr, *w = nullptr, *lval = nullptr, *part = nullptr;
+    int *lidx = nullptr, *seg_cnt = nullptr;
+    unsigned* nnz = nullptr;  // length of the list the last k_ista_axpy summed
+    int64_t N = 0;            // atoms the buffers were made for (0: none)
+    int Mv = 0, P = 0;        // ... and the column length and workgroup count of the partials
+};
+
 struct csmp_ctx;
 // Subspace Pursuit as a resumable job: see host/gomp_sp.hpp
 struct SpJob {
@@ -235,6 +245,7 @@ struct csmp_ctx {
     int tick_nblk = 0;       // absolute override of the sweep workgroup count (CSMP_TICK_NBLK), 0 = per-CU rule
     bool tick_sweep_first = false;  // dispatch the sweep workgroups ahead of the append stages (CSMP_TICK_ORDER=1)
     Batch bt;
+    IstaBuf ista;
     // profiling
     bool prof = false;
     int prof_every = 1;       // time every n-th sweep launch only (an event pair costs a few us of stream time)

@@ -244,6 +244,7 @@ static int dict_forget(csmp_ctx* ctx) {
         solver_free(ctx->s);
     }
     batch_free(ctx->bt, false);
+    ista_free(ctx->ista);
     return CSMP_OK;
 }
 

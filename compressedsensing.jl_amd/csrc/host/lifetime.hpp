@@ -81,6 +81,11 @@ static void solver_free(Solver& s) {
     s = Solver();
 }
 
+static void ista_free(IstaBuf& t) {
+    dfree(t.x); dfree(t.y); dfree(t.w); dfree(t.lval); dfree(t.part); dfree(t.lidx); dfree(t.seg_cnt); dfree(t.nnz);
+    t = IstaBuf();
+}
+
 static void dict_release(csmp_ctx* ctx) {
     if (ctx->share && --ctx->share->refs == 0) {
         if (ctx->share->kind == 0) (void)hipFree(ctx->share->p);
@@ -103,6 +108,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
         solver_free(ctx->s);
     }
     batch_free(ctx->bt, false);
+    ista_free(ctx->ista);
     if (ctx->comm) (void)csmp_comm_free(ctx);
     for (auto& t : ctx->twins) {
         if (t) (void)csmp_destroy(t);

@@ -160,6 +160,30 @@ function mp(A::MatOrDict{T}, b::AbstractVector, k::Int, x::SparseVector = spzero
     return x
 end
 
+# ---------------------------------------------------------------------------------- ista / fista
+# src/basispursuit.jl:144,164-204: x <- shrinkage(x + 2α A'(b - A x), wα) on ‖b - A x‖² + Σ w_j |x_j|, exactly maxiter times.
+# fista is the Beck-Teboulle acceleration of the same iteration (the reference's own, :186-204, does not run).
+shrinkage(x::Real, α::Real) = sign(x) * max(abs(x) - α, zero(x))
+function ista_call(A::MatOrDict, b::AbstractVector, w::Vector{Float64}, x::AbstractVector, maxiter::Int, stepsize::Real, accel::Bool)
+    D = dict(A)
+    bb, bt = bvec(b)
+    x0 = sparse(x)
+    idx0, val0 = convert(Vector{Int64}, x0.nzind .- 1), convert(Vector{Float64}, x0.nzval)
+    xd, rn = zeros(Float64, size(D, 2)), Ref{Cdouble}(0)
+    GC.@preserve bb w idx0 val0 xd check(D, ccall((:csmp_ista, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Cdouble}, Int64, Int64, Cdouble, Cint, Ptr{Cdouble}, Cint, Ref{Cdouble}),
+        D.ctx, bb, bt, w, length(w), idx0, val0, length(idx0), maxiter, stepsize, Cint(accel), xd, CSMP_HOST, rn))
+    return sparse(xd)  # (exact zeros are structural zeros: dropzeros!, :180)
+end
+ista(A::MatOrDict, b::AbstractVector, w::AbstractVector, x::AbstractVector = spzeros(size(A, 2)); maxiter::Int = 1024, stepsize::Real = 1e-2) =
+    ista_call(A, b, convert(Vector{Float64}, w), x, maxiter, stepsize, false)
+ista(A::MatOrDict, b::AbstractVector, λ::Real, x::AbstractVector = spzeros(size(A, 2)); maxiter::Int = 1024, stepsize::Real = 1e-2) =
+    ista_call(A, b, Float64[λ], x, maxiter, stepsize, false)
+fista(A::MatOrDict, b::AbstractVector, w::AbstractVector, x::AbstractVector = spzeros(size(A, 2)); maxiter::Int = 1024, stepsize::Real = 1e-2) =
+    ista_call(A, b, convert(Vector{Float64}, w), x, maxiter, stepsize, true)
+fista(A::MatOrDict, b::AbstractVector, λ::Real, x::AbstractVector = spzeros(size(A, 2)); maxiter::Int = 1024, stepsize::Real = 1e-2) =
+    ista_call(A, b, Float64[λ], x, maxiter, stepsize, true)
+
 # ---------------------------------------------------------------------------------- sp
 # src/twostage.jl:87-101
 function sp(A::MatOrDict{T}, b::AbstractVector, k::Int, δ::Real = 1e-12; maxiter = 16k) where {T}

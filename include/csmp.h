@@ -371,6 +371,27 @@ int csmp_shard_range(int64_t nsig, int rank, int world, int64_t *lo, int64_t *hi
 int csmp_pack_results(const int64_t *idx, const double *val, const int64_t *nnz, int64_t k, int64_t nsig, double *packed);
 int csmp_unpack_results(const double *packed, int64_t k, int64_t nsig, int64_t *idx, double *val, int64_t *nnz);
 
+/* ------------------------------------------------------------------ l1-regularised least squares
+ * ista(A,b,w,x; maxiter, stepsize): src/basispursuit.jl:164-183, and FISTA (Beck-Teboulle) on the same objective -- the
+ * reference's own fista (:186-204) does not run.  Convention, the reference's exactly: the objective is
+ * ||b - A x||^2 + sum_j w_j |x_j|, one iteration is  g = A'(b - A y);  x+ = shrinkage(y + 2 stepsize g, w stepsize)  with
+ * shrinkage(u, a) = sign(u) max(|u| - a, 0) (:144), and there is no stopping rule: exactly maxiter iterations.  accel = 0 (ISTA):
+ * y = x.  accel = 1 (FISTA): t_1 = 1, t+ = (1 + sqrt(1 + 4 t^2)) / 2, y+ = x+ + ((t - 1) / t+) (x+ - x), y_1 = x_0.
+ * w, nw: nw = 1 is one weight lambda for every atom (ista(A,b,lambda::Real,...), :164), nw = size(A,2) one weight per atom;
+ * anything else: CSMP_EDIM.  w is a host array; the weights are non-negative and finite.
+ * idx0 / val0 / nnz0: the warm start x_0 (indices 0-based, in any order); nnz0 = 0: x_0 = 0.  maxiter = 0 returns the warm start.
+ * x: the DENSE result, Float64[size(A,2)]; an exact zero is a structural zero of the reference's result (dropzeros!, :180).
+ * x_loc says where x AND b live: CSMP_HOST, or CSMP_DEVICE (both device pointers; the call still returns with the work done).
+ * resnorm (may be NULL): ||b - A x||_2 of the returned x.
+ * Arithmetic: Float64 on the exactly promoted dictionary values; x, y and the residual are Float64.  The same call returns the
+ * same bits every time.  CSMP_EINVAL: maxiter < 0, a stepsize that is not finite and positive, a negative or non-finite weight,
+ * a warm-start index out of range or repeated.  CSMP_ESTATE: no dictionary -- and a host-streamed dictionary
+ * (CSMP_HOST_STREAMED), which this entry does not serve: every iteration reads the dictionary up to twice. */
+int csmp_ista(csmp_ctx *ctx, const void *b, int b_dtype, const double *w, int64_t nw,
+              const int64_t *idx0, const double *val0, int64_t nnz0,
+              int64_t maxiter, double stepsize, int accel,
+              double *x, int x_loc, double *resnorm);
+
 /* ------------------------------------------------------------------ primitives
  * argmaxinner!(P) / argmaxinner!(P,k): src/matchingpursuit.jl:181-193.  r: length-M Float64
  * host vector.  abs_corr (may be NULL): receives |A' r| (length N).  top_idx/top_val: the
