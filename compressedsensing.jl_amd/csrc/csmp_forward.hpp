@@ -227,22 +227,9 @@ __device__ __forceinline__ void fr_sweep_body(
         if (col >= N) col = -1;
     }
     flush();
-    if ((lane & 15) == 0) {
-        redv[wave * 4 + (lane >> 4)] = bestv;
-        redi[wave * 4 + (lane >> 4)] = besti;
-    }
+    argmax_put_rows(redv, redi, wave, lane, bestv, besti);
     __syncthreads();
-    if (tid == 0) {
-        double bv = redv[0];
-        int bi = redi[0];
-        for (int q = 1; q < 4 * NW; ++q)
-            if (better(redv[q], redi[q], bv, bi)) {
-                bv = redv[q];
-                bi = redi[q];
-            }
-        pval[bid] = bv;
-        pidx[bid] = bi;
-    }
+    if (tid == 0) argmax_reduce(redv, redi, 4 * NW, pval, pidx, bid);
 }
 
 inline size_t fr_sweep_lds_bytes(int Mv, int vec, int U, int nq) {

@@ -167,6 +167,147 @@ __device__ __forceinline__ int r_slot(int m) {  // index in doubles
 }
 
 // ---------------------------------------------------------------------------------------------
+// The parts the product sweeps below are built from.  Every body's promise of "the single body's bits" is a call of these.
+//
+// One residual -> one LDS image (r_slot layout, zeros from Mv to Mst) by a team of 256 threads, and ||r||^2 in a fixed per-thread
+// order (identical in every workgroup): thread t of the team takes the rows t, t + 256, ...  Returns t's partial sum.
+// The loads go out 16 at a time (a rolled loop waits for each in turn: ~6 us of a 150 us kernel at M = 4096).
+template <int VEC>
+__device__ __forceinline__ double stage_image(const int t, const int Mv, const int Mst, const double* __restrict__ r, double* img) {
+    constexpr int RP = 16;
+    double n2 = 0.0;
+    for (int m0 = t; m0 < Mst; m0 += RP * kSweepThreads) {
+        double rv[RP];
+#pragma unroll
+        for (int q = 0; q < RP; ++q) {
+            const int m = m0 + q * kSweepThreads;
+            rv[q] = m < Mv ? r[m] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < RP; ++q) {
+            const int m = m0 + q * kSweepThreads;
+            if (m < Mst) img[r_slot<VEC>(m)] = rv[q];
+            n2 = fma(rv[q], rv[q], n2);
+        }
+    }
+    return n2;
+}
+// ||r||^2 from the threads' partials: the shuffle ladder over a wave (every lane ends with the wave's total), ...
+__device__ __forceinline__ double wave_sum_shfl(double v) {
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, kWave);
+    return v;
+}
+// ... then, once a barrier has published the four wave totals red[0], red[stride], ...: (0 + 1) + (2 + 3), st->rnorm2 by thread 0 of
+// workgroup 0 (bid: the workgroup's number in its sweep), and the reference's test.  True: the residual is below eps, this sweep is
+// not wanted.
+__device__ __forceinline__ bool norm2_test(const double* red, const int stride, DevState* st, const double eps, const int check_eps, const int bid) {
+    const double n2 = (red[0] + red[stride]) + (red[2 * stride] + red[3 * stride]);
+    if (bid == 0 && threadIdx.x == 0) st->rnorm2 = n2;
+    if (check_eps && !(sqrt(n2) >= eps)) {  // norm(residual!) >= eps || break  (:79,:132)
+        if (bid == 0 && threadIdx.x == 0) st->done |= STOP_EPS;
+        return true;
+    }
+    return false;
+}
+// A single residual: lane 0 of every wave of the team parks its ladder total in red[wave], the barrier, the test.  (PRE: a barrier
+// in front too.)
+template <bool PRE>
+__device__ __forceinline__ bool norm2_finish(const double n2, double* red, const int wave, const int lane, const bool team, DevState* st,
+                                             const double eps, const int check_eps, const int bid) {
+    if constexpr (PRE) __syncthreads();
+    if (lane == 0 && team) red[wave] = n2;
+    __syncthreads();
+    return norm2_test(red, 1, st, eps, check_eps, bid);
+}
+// The arg-max epilogue.  A lane's columns arrive in increasing order, so its (bestv, besti) is its first maximum; after wave_xsum the
+// 16 lanes of a row agree.  Each wave stores its four rows' pairs, ...
+__device__ __forceinline__ void argmax_put_rows(double* redv, int* redi, const int wave, const int lane, const double bestv, const int besti) {
+    if ((lane & 15) == 0) {
+        redv[wave * 4 + (lane >> 4)] = bestv;
+        redi[wave * 4 + (lane >> 4)] = besti;
+    }
+}
+// ... and after a barrier ONE thread reduces n of them with better() in index order: the first maximum of the workgroup.
+__device__ __forceinline__ void argmax_reduce(const double* redv, const int* redi, const int n, double* __restrict__ pval, int* __restrict__ pidx,
+                                              const int bid) {
+    double bv = redv[0];
+    int bi = redi[0];
+    for (int q = 1; q < n; ++q)
+        if (better(redv[q], redi[q], bv, bi)) {
+            bv = redv[q];
+            bi = redi[q];
+        }
+    pval[bid] = bv;
+    pidx[bid] = bi;
+}
+// One unit's loads: U consecutive 64-lane loads of column `col` from vector first_vec on.  A lane whose rows lie past the column's
+// end CLAMPS its vector index to the column's last vector -- a load of valid memory, no predicate, no extra DRAM line -- and the
+// residual image multiplies it with a zero.  NT: nontemporal (A is streamed once per sweep and exceeds every cache).
+template <typename TA, int U, bool NT = true>
+__device__ __forceinline__ void load_unit(const TA* __restrict__ A, const int64_t col, const int64_t ld, const int first_vec, const int nvec,
+                                          const int lane, typename Vec<TA>::type (&b)[U]) {
+    using VT = typename Vec<TA>::type;
+    const VT* pc = reinterpret_cast<const VT*>(A + col * ld);
+    const int vb = first_vec + lane;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int v = vb + u * kWave;
+        const VT* q = pc + (v < nvec ? v : nvec - 1);
+        if constexpr (NT) b[u] = __builtin_nontemporal_load(q);
+        else b[u] = *q;
+    }
+}
+// c values are STAGED: lane s keeps the total of the wave's s-th finished column and the wave writes 64 of them with one
+// store instruction.  A store per column sits in the wave's in-order memory queue among the ring's loads: measured 1.5-3 us of
+// a 155-us sweep at 16-KiB columns, 5-7 % at 8-KiB Float64 columns, 13 us of 170 with one store per 4 KiB (short columns).
+// R residuals share the columns: one value each, stored where the member's bit of `live` is set.  IT: the column index type.
+template <int R = 1, typename IT = int64_t>
+struct CStage {
+    double cst[R];
+    IT ccst;
+    int cslot;
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int i = 0; i < R; ++i) cst[i] = 0.0;
+        ccst = -1;
+        cslot = 0;
+    }
+    // lane cslot + j takes a finished column: member i's total, the column's index (-1: nobody stores it); then n columns are taken
+    __device__ __forceinline__ void put(const int lane, const int i, const double v, const int j = 0) {
+        if (lane == cslot + j) cst[i] = v;
+    }
+    __device__ __forceinline__ void col(const int lane, const IT c, const int j = 0) {
+        if (lane == cslot + j) ccst = c;
+    }
+    __device__ __forceinline__ void next(const int n, double* const* cvec, const unsigned live) {
+        cslot += n;
+        if (cslot == kWave) flush(cvec, live);
+    }
+    __device__ __forceinline__ void flush(double* const* cvec, const unsigned live) {
+        if (ccst >= 0) {
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+                if (live & (1u << i)) cvec[i][ccst] = cst[i];
+        }
+        ccst = -1;
+        cslot = 0;
+    }
+    // the single residual
+    __device__ __forceinline__ void put(const int lane, const IT c, const double v, double* __restrict__ cvec) {
+        if (lane == cslot) {
+            cst[0] = v;
+            ccst = c;
+        }
+        if (++cslot == kWave) flush(cvec);
+    }
+    __device__ __forceinline__ void flush(double* __restrict__ cvec) {
+        if (ccst >= 0) cvec[ccst] = cst[0];
+        ccst = -1;
+        cslot = 0;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
 // Sweep: c = A' r (Float64), fused |.| + arg-max partials (argmaxinner!(P), src/matchingpursuit.jl:181-185).  One wave owns ONE
 // whole column at a time (16 KiB contiguous at M = 4096 f32), lanes stride the rows with 16-byte non-temporal loads (A is streamed
 // once per sweep and exceeds every cache), r lives in the LDS.  Grid-stride over columns; one (max |c|, first index) pair per
@@ -177,8 +318,7 @@ __device__ __forceinline__ int r_slot(int m) {  // index in doubles
 //   ring    NB units in flight per wave, consumed oldest first; a consumed buffer is refilled at once with the unit NB ahead.
 //           In the steady loop every load is unconditional (no branch around a load), so the wait the compiler places in front
 //           of a unit's arithmetic is s_waitcnt vmcnt((NB-1)*U): the wave never drains below (NB-1)*U KiB in flight.
-//   ragged  a lane whose rows lie past the column's end CLAMPS its vector index to the column's last vector -- a load of valid
-//           memory, no predicate, no extra DRAM line -- and multiplies it with a zero of the residual image.
+//   ragged  a lane whose rows lie past the column's end loads the column's last vector instead (load_unit).
 // KP: rows of the residual image (a multiple of U*64*VEC, >= Mv).  dynamic LDS: KP doubles + 32 doubles of scratch.
 template <typename TA, int U, int NB>
 __device__ __forceinline__ void sweep_body_gen(
@@ -208,25 +348,15 @@ __device__ __forceinline__ void sweep_body_gen(
     const int nunit = (Mv + UR - 1) / UR;  // units per column
     const int Mst = nunit * UR;            // rows of the image in use (zero beyond Mv)
     VT buf[NB][U];
-    // c values are STAGED: lane s keeps the total of the wave's s-th finished column and the wave writes 64 of them with one
-    // store instruction.  A store per column sits in the wave's in-order memory queue among the ring's loads: measured 1.5-3 us of
-    // a 155-us sweep at 16-KiB columns, 5-7 % at 8-KiB Float64 columns, 13 us of 170 with one store per 4 KiB (short columns).
-    double cst = 0.0;
-    int64_t ccst = -1;
-    int cslot = 0;
+    CStage<> cs;
+    cs.init();
     int64_t icol = col0, ccol = col0;  // issue / consume pointers: (column, unit within the column)
     int ib = 0, cb = 0;
     const int64_t T = ncol * nunit;
     int64_t ileft = T, cleft = T;
     double acc = 0.0;
     auto issue = [&](VT(&b)[U]) {
-        const VT* pc = reinterpret_cast<const VT*>(A + icol * ld);
-        const int vb = ib * (U * kWave) + lane;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int v = vb + u * kWave;
-            b[u] = __builtin_nontemporal_load(pc + (v < nvec ? v : nvec - 1));
-        }
+        load_unit<TA, U>(A, icol, ld, ib * (U * kWave), nvec, lane, b);
         if (++ib == nunit) {
             ib = 0;
             icol += stride;
@@ -244,11 +374,10 @@ __device__ __forceinline__ void sweep_body_gen(
         }
         issue(buf[d]);
     }
+    // (stage_image and wave_sum_shfl written out: as calls they cost this body, and k_tick with it, one VGPR on Float32)
+    double n2 = 0.0;
     {
-        // the residual image, and ||r||^2 in a fixed per-thread order (identical in every workgroup).
-        // The loads go out 16 at a time (a rolled loop waits for each in turn: ~6 us of a 150 us kernel at M = 4096).
         constexpr int RP = 16;
-        double n2 = 0.0;
         for (int m0 = tid; m0 < Mst; m0 += RP * kSweepThreads) {
             double rv[RP];
 #pragma unroll
@@ -264,16 +393,8 @@ __device__ __forceinline__ void sweep_body_gen(
             }
         }
         for (int s = 32; s >= 1; s >>= 1) n2 += __shfl_xor(n2, s, kWave);
-        __syncthreads();
-        if (lane == 0) red[wave] = n2;
-        __syncthreads();
-        n2 = (red[0] + red[1]) + (red[2] + red[3]);
-        if (bid == 0 && tid == 0) st->rnorm2 = n2;
-        if (check_eps && !(sqrt(n2) >= eps)) {  // norm(residual!) >= eps || break  (:79,:132)
-            if (bid == 0 && tid == 0) st->done |= STOP_EPS;
-            return;
-        }
     }
+    if (norm2_finish<true>(n2, red, wave, lane, true, st, eps, check_eps, bid)) return;
     PH_STAMP(1);
     auto consume = [&](const VT(&b)[U]) {
 #pragma unroll
@@ -294,15 +415,7 @@ __device__ __forceinline__ void sweep_body_gen(
         }
         if (++cb == nunit) {  // the column's last unit
             acc = wave_xsum(acc);
-            if (lane == cslot) {
-                cst = acc;
-                ccst = ccol;
-            }
-            if (++cslot == kWave) {
-                if (ccst >= 0) cvec[ccst] = cst;
-                ccst = -1;
-                cslot = 0;
-            }
+            cs.put(lane, ccol, acc, cvec);
             const double av = fabs(acc);
             if (av > bestv) {  // columns arrive in increasing order: '>' keeps the first maximum
                 bestv = av;
@@ -332,24 +445,11 @@ __device__ __forceinline__ void sweep_body_gen(
             if (ileft > 0) issue(buf[d]);
         }
     }
-    if (ccst >= 0) cvec[ccst] = cst;  // (the columns staged since the last full store)
+    cs.flush(cvec);  // (the columns staged since the last full store)
     PH_STAMP(5);
-    if ((lane & 15) == 0) {
-        redv[wave * 4 + (lane >> 4)] = bestv;
-        redi[wave * 4 + (lane >> 4)] = besti;
-    }
+    argmax_put_rows(redv, redi, wave, lane, bestv, besti);
     __syncthreads();
-    if (tid == 0) {
-        double bv = redv[0];
-        int bi = redi[0];
-        for (int q = 1; q < 4 * NW; ++q)
-            if (better(redv[q], redi[q], bv, bi)) {
-                bv = redv[q];
-                bi = redi[q];
-            }
-        pval[bid] = bv;
-        pidx[bid] = bi;
-    }
+    if (tid == 0) argmax_reduce(redv, redi, 4 * NW, pval, pidx, bid);
 }
 template <typename TA, int U, int NB>
 __global__ __launch_bounds__(kSweepThreads) void k_sweep_gen(
@@ -413,7 +513,7 @@ __device__ __forceinline__ void sweep_body_ph(
     };
     // the image of stage ph: pairs of rows (16-byte loads; a pair is one 16-byte LDS slot in either layout), 16 loads in flight per
     // thread -- one by one a stage of 16 384 rows is 64 dependent trips per thread, and the stage's barrier waits for all of them
-    auto stage_image = [&](int ph, double& n2, auto rp) {
+    auto stage_pairs = [&](int ph, double& n2, auto rp) {
         const int k0 = ph * KP, Mst = units_of(ph) * UR;
         const int Mend = Mst;  // (||r||^2 grows stage by stage: thread t adds the pairs of rows with (m / 2) mod 256 = t in increasing order)
         constexpr int RP = decltype(rp)::value;
@@ -447,13 +547,7 @@ __device__ __forceinline__ void sweep_body_ph(
     int64_t icol = col0 < N ? col0 : N - 1;
     int ik0v = 0;
     auto issue = [&](VT(&b)[U], int& s_, int& b_) {
-        const VT* pc = reinterpret_cast<const VT*>(A + icol * ld);
-        const int vb = ik0v + ib * (U * kWave) + lane;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int v = vb + u * kWave;
-            b[u] = __builtin_nontemporal_load(pc + (v < nvec ? v : nvec - 1));
-        }
+        load_unit<TA, U>(A, icol, ld, ik0v + ib * (U * kWave), nvec, lane, b);
         const bool real = irem > 0;
         s_ = real ? is : -1;
         b_ = ib;
@@ -479,9 +573,8 @@ __device__ __forceinline__ void sweep_body_ph(
         }
     };
     double acc = 0.0;
-    double cst = 0.0;  // c values staged 64 to a store instruction (see sweep_body_gen)
-    int64_t ccst = -1;
-    int cslot = 0;
+    CStage<> cs;
+    cs.init();
     // the ring's first loads go out before the first image is staged (see sweep_body_gen)
 #pragma unroll
     for (int d = 0; d < NB; ++d) issue(buf[d], ms[d], mb[d]);
@@ -489,19 +582,10 @@ __device__ __forceinline__ void sweep_body_ph(
     // keep -- the whole residual in the first stage was 2 of its 4 trips, ~4.5 us of a 165-us launch at M = 32768); the eps test
     // waits for it.  A sweep that turns out not to be wanted has then run all but its last stage: nobody looks at its results.
     double n2 = 0.0;
-    auto norm_done = [&]() -> bool {  // (after the image's stores, before the barrier that publishes it)
-        for (int s = 32; s >= 1; s >>= 1) n2 += __shfl_xor(n2, s, kWave);
-        if (lane == 0) red[wave] = n2;
-        __syncthreads();
-        n2 = (red[0] + red[1]) + (red[2] + red[3]);
-        if (bid == 0 && tid == 0) st->rnorm2 = n2;
-        if (check_eps && !(sqrt(n2) >= eps)) {  // norm(residual!) >= eps || break  (:79,:132)
-            if (bid == 0 && tid == 0) st->done |= STOP_EPS;
-            return true;
-        }
-        return false;
+    auto norm_done = [&]() -> bool {  // (after the image's stores; its barrier publishes the image too)
+        return norm2_finish<false>(wave_sum_shfl(n2), red, wave, lane, true, st, eps, check_eps, bid);
     };
-    stage_image(0, n2, std::integral_constant<int, 16>());
+    stage_pairs(0, n2, std::integral_constant<int, 16>());
     if (nph == 1) {
         if (norm_done()) return;
     } else {
@@ -513,7 +597,7 @@ __device__ __forceinline__ void sweep_body_ph(
             PH_STAMP(2);
             lds_barrier();  // everyone is done with the previous image (the ring's loads stay in flight)
             PH_STAMP(3);
-            stage_image(ph, n2, std::integral_constant<int, 16>());
+            stage_pairs(ph, n2, std::integral_constant<int, 16>());
             if (ph + 1 == nph) {
                 if (norm_done()) return;
             } else {
@@ -551,15 +635,7 @@ __device__ __forceinline__ void sweep_body_ph(
                             if (lane == 0) part[ms[d]] = acc;
                         } else {
                             const int64_t col = col0 + (int64_t)ms[d] * stride;
-                            if (lane == cslot) {
-                                cst = acc;
-                                ccst = col;
-                            }
-                            if (++cslot == kWave) {
-                                if (ccst >= 0) cvec[ccst] = cst;
-                                ccst = -1;
-                                cslot = 0;
-                            }
+                            cs.put(lane, col, acc, cvec);
                             const double av = fabs(acc);
                             if (av > bestv) {  // columns arrive in increasing order: '>' keeps the first maximum
                                 bestv = av;
@@ -573,24 +649,11 @@ __device__ __forceinline__ void sweep_body_ph(
             }
         }
     }
-    if (ccst >= 0) cvec[ccst] = cst;
+    cs.flush(cvec);
     PH_STAMP(5);
-    if ((lane & 15) == 0) {
-        redv[wave * 4 + (lane >> 4)] = bestv;
-        redi[wave * 4 + (lane >> 4)] = besti;
-    }
+    argmax_put_rows(redv, redi, wave, lane, bestv, besti);
     __syncthreads();
-    if (tid == 0) {
-        double bv = redv[0];
-        int bi = redi[0];
-        for (int q = 1; q < 4 * NW; ++q)
-            if (better(redv[q], redi[q], bv, bi)) {
-                bv = redv[q];
-                bi = redi[q];
-            }
-        pval[bid] = bv;
-        pidx[bid] = bi;
-    }
+    if (tid == 0) argmax_reduce(redv, redi, 4 * NW, pval, pidx, bid);
 }
 template <typename TA, int U, int NB>
 __global__ __launch_bounds__(kSweepThreads) void k_sweep_ph(
@@ -684,16 +747,7 @@ __device__ __forceinline__ void sweep_body_short(
             lds[r_slot<VEC>(m)] = rv;
             n2 = fma(rv, rv, n2);
         }
-        for (int s = 32; s >= 1; s >>= 1) n2 += __shfl_xor(n2, s, kWave);
-        __syncthreads();
-        if (lane == 0) red[wave] = n2;
-        __syncthreads();
-        n2 = (red[0] + red[1]) + (red[2] + red[3]);
-        if (bid == 0 && tid == 0) st->rnorm2 = n2;
-        if (check_eps && !(sqrt(n2) >= eps)) {  // norm(residual!) >= eps || break  (:79,:132)
-            if (bid == 0 && tid == 0) st->done |= STOP_EPS;
-            return;
-        }
+        if (norm2_finish<true>(wave_sum_shfl(n2), red, wave, lane, true, st, eps, check_eps, bid)) return;
     }
     PH_STAMP(1);
     auto consume = [&](const VT(&b)[U]) {
@@ -737,7 +791,7 @@ __device__ __forceinline__ void sweep_body_short(
                 }
             }
         }
-        // the c values are staged (see sweep_body_gen): the LW = 64 / CPU lanes that hold a column's total are SETS x SLOTS; lane
+        // the c values are staged (see CStage): the LW = 64 / CPU lanes that hold a column's total are SETS x SLOTS; lane
         // (q, set, slot) keeps column set * CPU + q of the unit whose number is slot mod SLOTS, and every SLOTS units all 64 lanes store
         {
             const int set = (lane & (LW - 1)) / SLOTS, slot = (lane & (LW - 1)) % SLOTS;
@@ -783,22 +837,9 @@ __device__ __forceinline__ void sweep_body_short(
     }
     flush();
     PH_STAMP(5);
-    if ((lane & 15) == 0) {
-        redv[wave * 4 + (lane >> 4)] = bestv;
-        redi[wave * 4 + (lane >> 4)] = besti;
-    }
+    argmax_put_rows(redv, redi, wave, lane, bestv, besti);
     __syncthreads();
-    if (tid == 0) {
-        double bv = redv[0];
-        int bi = redi[0];
-        for (int qq = 1; qq < 4 * NW; ++qq)
-            if (better(redv[qq], redi[qq], bv, bi)) {
-                bv = redv[qq];
-                bi = redi[qq];
-            }
-        pval[bid] = bv;
-        pidx[bid] = bi;
-    }
+    if (tid == 0) argmax_reduce(redv, redi, 4 * NW, pval, pidx, bid);
 }
 template <typename TA, int NCH, int CPU>
 __global__ __launch_bounds__(kSweepThreads) void k_sweep_short(
@@ -878,34 +919,9 @@ __device__ __forceinline__ void sweep_body_dyn(
     const int Mst = nunit * UR;
     if (tid < NW * Q) q_store(q + tid, kClEmpty);
     {
-        constexpr int RP = 16;
         double n2 = 0.0;
-        if (wave < NW) {
-            for (int m0 = tid; m0 < Mst; m0 += RP * kSweepThreads) {
-                double rv[RP];
-#pragma unroll
-                for (int qq = 0; qq < RP; ++qq) {
-                    const int m = m0 + qq * kSweepThreads;
-                    rv[qq] = m < Mv ? r[m] : 0.0;
-                }
-#pragma unroll
-                for (int qq = 0; qq < RP; ++qq) {
-                    const int m = m0 + qq * kSweepThreads;
-                    if (m < Mst) lds[r_slot<VEC>(m)] = rv[qq];
-                    n2 = fma(rv[qq], rv[qq], n2);
-                }
-            }
-            for (int s = 32; s >= 1; s >>= 1) n2 += __shfl_xor(n2, s, kWave);
-        }
-        __syncthreads();
-        if (lane == 0 && wave < NW) red[wave] = n2;
-        __syncthreads();
-        n2 = (red[0] + red[1]) + (red[2] + red[3]);
-        if (bid == 0 && tid == 0) st->rnorm2 = n2;
-        if (check_eps && !(sqrt(n2) >= eps)) {  // norm(residual!) >= eps || break  (:79,:132)
-            if (bid == 0 && tid == 0) st->done |= STOP_EPS;
-            return;
-        }
+        if (wave < NW) n2 = wave_sum_shfl(stage_image<VEC>(tid, Mv, Mst, r, lds));  // (the four streaming waves are the team)
+        if (norm2_finish<true>(n2, red, wave, lane, wave < NW, st, eps, check_eps, bid)) return;
     }
     if (wave == NW) {
         // ---- the claimer: lane w < 4 serves streaming wave w
@@ -968,8 +984,8 @@ __device__ __forceinline__ void sweep_body_dyn(
     int icol = 0, ib = 0, ipos = 0;
     bool live = true;
     double acc = 0.0;
-    double cst = 0.0;  // c values staged 64 to a store instruction (see sweep_body_gen)
-    int ccst = -1, cslot = 0;
+    CStage<1, int> cs;
+    cs.init();
     lds_int_ptr myq = q + wave * Q;
     auto issue = [&](VT(&b)[U], int& c_, int& u_) {
         if (ib == 0 && live) {
@@ -988,6 +1004,7 @@ __device__ __forceinline__ void sweep_body_dyn(
                 icol = c;
             }
         }
+        // (load_unit with a second clamp: after END every lane reads vector 0 of column 0)
         const VT* pc = reinterpret_cast<const VT*>(A + (live ? (int64_t)icol * ld : 0));
         const int vb = ib * (U * kWave) + lane;
 #pragma unroll
@@ -1019,15 +1036,7 @@ __device__ __forceinline__ void sweep_body_dyn(
         }
         if (u_ == nunit - 1) {  // the column's last unit
             acc = wave_xsum(acc);
-            if (lane == cslot) {
-                cst = acc;
-                ccst = c_;
-            }
-            if (++cslot == kWave) {
-                if (ccst >= 0) cvec[ccst] = cst;
-                ccst = -1;
-                cslot = 0;
-            }
+            cs.put(lane, c_, acc, cvec);
             const double av = fabs(acc);
             if (better(av, c_, bestv, besti)) {
                 bestv = av;
@@ -1047,23 +1056,13 @@ __device__ __forceinline__ void sweep_body_dyn(
     }
 #pragma unroll
     for (int d = 0; d < NB; ++d) consume(buf[d], bc[d], bu[d]);
-    if (ccst >= 0) cvec[ccst] = cst;
-    if (lane == 0) {
+    cs.flush(cvec);
+    if (lane == 0) {  // (one pair per wave: its lanes agree)
         redv[wave] = bestv;
         redi[wave] = besti;
     }
     lds_barrier();  // (the claimer has left: a barrier counts the waves that are still running)
-    if (tid == 0) {
-        double bv = redv[0];
-        int bi = redi[0];
-        for (int qq = 1; qq < NW; ++qq)
-            if (better(redv[qq], redi[qq], bv, bi)) {
-                bv = redv[qq];
-                bi = redi[qq];
-            }
-        pval[bid] = bv;
-        pidx[bid] = bi;
-    }
+    if (tid == 0) argmax_reduce(redv, redi, NW, pval, pidx, bid);
 }
 template <typename TA, int U, int NB>
 __global__ __launch_bounds__(kSweepDynThreads) void k_sweep_dyn(
@@ -2109,7 +2108,7 @@ __global__ __launch_bounds__(DYN ? kSweepDynThreads : kSweepThreads) void k_tick
 //           registers are refilled with the unit NB ahead as soon as the load is converted.
 //   f64     Float64 dictionaries keep round 7's four-wave body (sweep_body_multi_w4 below).
 //   norm    member i's image and ||r||^2 are staged by the half of the workgroup i & 1 names: its 256 threads run
-//           sweep_body_gen's loop over t = tid & 255 -- every thread's partial sum, and the sums over the four waves of the half,
+//           stage_image with t = tid & 255 -- every thread's partial sum, and the sums over the four waves of the half,
 //           are the single body's.
 // dynamic LDS: R images of KP doubles + the scratch (sweep_multi_lds_bytes).
 constexpr int kGroupMax = 4;             // images per workgroup
@@ -2163,16 +2162,15 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
     const int nunit = KP / UR;  // every row of the image, as sweep_body_gen runs them (its KP is a whole number of 4-load units)
     const int Mst = KP;
     VT buf[NB][2][U];
-    double cst[R], acc[2][R];
+    double acc[2][R];
 #pragma unroll
     for (int i = 0; i < R; ++i) {
         bestv[i] = -1.0;
         besti[i] = 0x7fffffff;
-        cst[i] = 0.0;
         acc[0][i] = acc[1][i] = 0.0;
     }
-    int64_t ccst = -1;
-    int cslot = 0;
+    CStage<R> cs;
+    cs.init();
     int64_t iq = q0, cq = q0;
     int ib = 0, cb = 0;
     const int64_t T = npair * nunit;
@@ -2183,6 +2181,7 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
     };
     auto issue = [&](VT(&b)[2][U]) {
         const int64_t c0 = 2 * iq, c1 = c0 + 1 < N ? c0 + 1 : N - 1;
+        // (load_unit's loads for both columns, interleaved: the pair's first requests go out together)
         const VT* p0 = reinterpret_cast<const VT*>(A + c0 * ld);
         const VT* p1 = reinterpret_cast<const VT*>(A + c1 * ld);
         const int vb = ib * (U * kWave) + lane;
@@ -2207,33 +2206,17 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
         issue(buf[d]);
     }
     {
-        // the images and every member's ||r||^2, each in sweep_body_gen's per-thread order (t: the thread's index in its half)
-        constexpr int RP = 16;
+        // the images and every member's ||r||^2: member i's team is the half of the workgroup that i & 1 names
         const int half = wave >> 2, t = tid & (kSweepThreads - 1);
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             if ((i & 1) != half) continue;
-            const double* __restrict__ r = p.r[mo + i];
-            double* img = lds + (size_t)i * KP;
-            double n2 = 0.0;
-            for (int m0 = t; m0 < Mst; m0 += RP * kSweepThreads) {
-                double rv[RP];
-#pragma unroll
-                for (int q = 0; q < RP; ++q) {
-                    const int m = m0 + q * kSweepThreads;
-                    rv[q] = m < Mv ? r[m] : 0.0;
-                }
-#pragma unroll
-                for (int q = 0; q < RP; ++q) {
-                    const int m = m0 + q * kSweepThreads;
-                    if (m < Mst) img[r_slot<VEC>(m)] = rv[q];
-                    n2 = fma(rv[q], rv[q], n2);
-                }
-            }
-            for (int s = 32; s >= 1; s >>= 1) n2 += __shfl_xor(n2, s, kWave);
+            const double n2 = wave_sum_shfl(stage_image<VEC>(t, Mv, Mst, p.r[mo + i], lds + (size_t)i * KP));
             if (lane == 0) n2s[(wave & 3) * R + i] = n2;
         }
         __syncthreads();
+        // (norm2_test's statements, stride R, written out: as a call they cost this body up to five registers, and its kernels are
+        // bound to two waves per SIMD)
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             if (!(live & (1u << i))) continue;
@@ -2324,7 +2307,7 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
                     const double c = wave_xsum(acc[j][i]);
                     acc[j][i] = 0.0;
                     if (j == 1 && !two) continue;
-                    if (lane == cslot + j) cst[i] = c;
+                    cs.put(lane, i, c, j);
                     const double av = fabs(c);
                     if (av > bestv[i]) {  // columns arrive in increasing order: '>' keeps the first maximum
                         bestv[i] = av;
@@ -2332,18 +2315,9 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
                     }
                 }
             }
-            if (lane == cslot) ccst = c0;
-            if (lane == cslot + 1) ccst = two ? c0 + 1 : -1;
-            cslot += 2;
-            if (cslot == kWave) {
-                if (ccst >= 0) {
-#pragma unroll
-                    for (int i = 0; i < R; ++i)
-                        if (live & (1u << i)) p.cvec[mo + i][ccst] = cst[i];
-                }
-                ccst = -1;
-                cslot = 0;
-            }
+            cs.col(lane, c0);
+            cs.col(lane, two ? c0 + 1 : -1, 1);
+            cs.next(2, p.cvec + mo, live);
             cb = 0;
             cq += stride;
         }
@@ -2364,32 +2338,12 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
             if (ileft > 0) issue(buf[d]);
         }
     }
-    if (ccst >= 0) {
+    cs.flush(p.cvec + mo, live);
 #pragma unroll
-        for (int i = 0; i < R; ++i)
-            if (live & (1u << i)) p.cvec[mo + i][ccst] = cst[i];
-    }
-    if ((lane & 15) == 0) {
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            redv[i * 4 * NW + wave * 4 + (lane >> 4)] = bestv[i];
-            redi[i * 4 * NW + wave * 4 + (lane >> 4)] = besti[i];
-        }
-    }
+    for (int i = 0; i < R; ++i) argmax_put_rows(redv + i * 4 * NW, redi + i * 4 * NW, wave, lane, bestv[i], besti[i]);
     __syncthreads();
-    if (tid < R && (live & (1u << tid))) {  // thread i reduces member i's partials with better(): the first maximum of the workgroup
-        const double* rv = redv + tid * 4 * NW;
-        const int* ri = redi + tid * 4 * NW;
-        double bv = rv[0];
-        int bi = ri[0];
-        for (int q = 1; q < 4 * NW; ++q)
-            if (better(rv[q], ri[q], bv, bi)) {
-                bv = rv[q];
-                bi = ri[q];
-            }
-        p.pval[mo + tid][bid] = bv;
-        p.pidx[mo + tid][bid] = bi;
-    }
+    if (tid < R && (live & (1u << tid)))  // thread i reduces member i's partials
+        argmax_reduce(redv + tid * 4 * NW, redi + tid * 4 * NW, 4 * NW, p.pval[mo + tid], p.pidx[mo + tid], bid);
 }
 // U loads per column and unit, NB = 2 units in the ring
 template <typename TA, int U, int R>
@@ -2444,28 +2398,21 @@ __device__ __forceinline__ void sweep_body_multi_w4(const MultiSweep<TA>& p, con
     const int nunit = (Mv + UR - 1) / UR;
     const int Mst = nunit * UR;
     VT buf[NB][U];
-    double cst[R], acc[R];
+    double acc[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) {
         bestv[i] = -1.0;
         besti[i] = 0x7fffffff;
-        cst[i] = 0.0;
         acc[i] = 0.0;
     }
-    int64_t ccst = -1;
-    int cslot = 0;
+    CStage<R> cs;
+    cs.init();
     int64_t icol = col0, ccol = col0;
     int ib = 0, cb = 0;
     const int64_t T = ncol * nunit;
     int64_t ileft = T, cleft = T;
     auto issue = [&](VT(&b)[U]) {
-        const VT* pc = reinterpret_cast<const VT*>(A + icol * ld);
-        const int vb = ib * (U * kWave) + lane;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int v = vb + u * kWave;
-            b[u] = __builtin_nontemporal_load(pc + (v < nvec ? v : nvec - 1));
-        }
+        load_unit<TA, U>(A, icol, ld, ib * (U * kWave), nvec, lane, b);
         if (++ib == nunit) {
             ib = 0;
             icol += stride;
@@ -2481,31 +2428,14 @@ __device__ __forceinline__ void sweep_body_multi_w4(const MultiSweep<TA>& p, con
         issue(buf[d]);
     }
     {
-        // the images and every member's ||r||^2, each in sweep_body_gen's per-thread order
-        constexpr int RP = 16;
+        // the images and every member's ||r||^2
 #pragma unroll
         for (int i = 0; i < R; ++i) {
-            const double* __restrict__ r = p.r[i];
-            double* img = lds + (size_t)i * KP;
-            double n2 = 0.0;
-            for (int m0 = tid; m0 < Mst; m0 += RP * kSweepThreads) {
-                double rv[RP];
-#pragma unroll
-                for (int q = 0; q < RP; ++q) {
-                    const int m = m0 + q * kSweepThreads;
-                    rv[q] = m < Mv ? r[m] : 0.0;
-                }
-#pragma unroll
-                for (int q = 0; q < RP; ++q) {
-                    const int m = m0 + q * kSweepThreads;
-                    if (m < Mst) img[r_slot<VEC>(m)] = rv[q];
-                    n2 = fma(rv[q], rv[q], n2);
-                }
-            }
-            for (int s = 32; s >= 1; s >>= 1) n2 += __shfl_xor(n2, s, kWave);
+            const double n2 = wave_sum_shfl(stage_image<VEC>(tid, Mv, Mst, p.r[i], lds + (size_t)i * KP));
             if (lane == 0) n2s[wave * R + i] = n2;
         }
         __syncthreads();
+        // (norm2_test's statements, stride R, written out: as a call they cost this body one to five VGPRs)
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             if (!(live & (1u << i))) continue;
@@ -2549,7 +2479,7 @@ __device__ __forceinline__ void sweep_body_multi_w4(const MultiSweep<TA>& p, con
 #pragma unroll
             for (int i = 0; i < R; ++i) {
                 const double c = wave_xsum(acc[i]);
-                if (lane == cslot) cst[i] = c;
+                cs.put(lane, i, c);
                 const double av = fabs(c);
                 if (av > bestv[i]) {  // columns arrive in increasing order: '>' keeps the first maximum
                     bestv[i] = av;
@@ -2557,16 +2487,8 @@ __device__ __forceinline__ void sweep_body_multi_w4(const MultiSweep<TA>& p, con
                 }
                 acc[i] = 0.0;
             }
-            if (lane == cslot) ccst = ccol;
-            if (++cslot == kWave) {
-                if (ccst >= 0) {
-#pragma unroll
-                    for (int i = 0; i < R; ++i)
-                        if (live & (1u << i)) p.cvec[i][ccst] = cst[i];
-                }
-                ccst = -1;
-                cslot = 0;
-            }
+            cs.col(lane, ccol);
+            cs.next(1, p.cvec, live);
             cb = 0;
             ccol += stride;
         }
@@ -2590,32 +2512,12 @@ __device__ __forceinline__ void sweep_body_multi_w4(const MultiSweep<TA>& p, con
             if (ileft > 0) issue(buf[d]);
         }
     }
-    if (ccst >= 0) {
+    cs.flush(p.cvec, live);
 #pragma unroll
-        for (int i = 0; i < R; ++i)
-            if (live & (1u << i)) p.cvec[i][ccst] = cst[i];
-    }
-    if ((lane & 15) == 0) {
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            redv[i * 4 * NW + wave * 4 + (lane >> 4)] = bestv[i];
-            redi[i * 4 * NW + wave * 4 + (lane >> 4)] = besti[i];
-        }
-    }
+    for (int i = 0; i < R; ++i) argmax_put_rows(redv + i * 4 * NW, redi + i * 4 * NW, wave, lane, bestv[i], besti[i]);
     __syncthreads();
-    if (tid < R && (live & (1u << tid))) {  // thread i reduces member i's partials in sweep_body_gen's order
-        const double* rv = redv + tid * 4 * NW;
-        const int* ri = redi + tid * 4 * NW;
-        double bv = rv[0];
-        int bi = ri[0];
-        for (int q = 1; q < 4 * NW; ++q)
-            if (better(rv[q], ri[q], bv, bi)) {
-                bv = rv[q];
-                bi = ri[q];
-            }
-        p.pval[tid][bid] = bv;
-        p.pidx[tid][bid] = bi;
-    }
+    if (tid < R && (live & (1u << tid)))  // thread i reduces member i's partials
+        argmax_reduce(redv + tid * 4 * NW, redi + tid * 4 * NW, 4 * NW, p.pval[tid], p.pidx[tid], bid);
 }
 template <typename TA, int U, int R>
 __global__ __launch_bounds__(kSweepThreads) void k_sweep_multi_w4(const MultiSweep<TA> p) {
