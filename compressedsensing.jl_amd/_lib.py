@@ -82,6 +82,8 @@ SIGNATURES = {
     "csmp_solver_remove": (C.c_int, [vp, i64]),
     "csmp_solver_state": (C.c_int, [vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp, C.POINTER(C.c_int)]),
     "csmp_ista": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, i64, i64, C.c_double, C.c_int, vp, C.c_int, C.POINTER(C.c_double)]),
+    "csmp_colnorms": (C.c_int, [vp, vp, C.c_int]),
+    "csmp_cumbabel": (C.c_int, [vp, i64, C.c_int, vp, vp]),
     "csmp_sweep": (C.c_int, [vp, vp, vp, i64, vp, vp]),
     "csmp_lstsq": (C.c_int, [vp, vp, i64, vp, C.c_int, vp]),
 }
@@ -105,6 +107,7 @@ INTERNAL_SIGNATURES = {
 TUNE = {"sweep_grid": 2, "sweep_unit": 3, "tick_grid": 4, "batch_budget_mib": 5, "diag_split": 6, "swap_refuse": 7, "rebuild_direct": 8, "sweep_dyn": 9, "tick_order": 10, "claim_pools": 11, "pipelines": 12, "pair_lds_kib": 13, "pair_split": 14, "sweep_lds_kib": 15, "sweep_short": 16, "phase_rows": 17, "fail_alloc": 18, "screen_static": 19, "group_max": 20, "group_wide": 21}  # CSMP_TUNE_* (include/csmp_internal.h)
 
 COMM_ID_BYTES = 128  # CSMP_COMM_ID_BYTES
+BABEL_KMAX = 1024  # CSMP_BABEL_KMAX
 
 
 def live_resources():
@@ -666,6 +669,26 @@ class Context:
         self.call("csmp_ista", vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64, ptr(w), i64(len(w)), ptr(idx0), ptr(val0),
                   i64(len(idx0)), i64(int(maxiter)), C.c_double(stepsize), int(bool(accel)), vp(x.data_ptr()), DEVICE, C.byref(rn))
         return rn.value
+
+    # ---- dictionary analysis
+    def colnorms(self, device=False):
+        """csmp_colnorms: ||a_j|| of every column, Float64[N] -- a numpy array, or (device=True) a torch CUDA tensor."""
+        if device:
+            import torch
+            out = torch.empty(max(self.N, 1), dtype=torch.float64, device="cuda")
+            self.call("csmp_colnorms", vp(out.data_ptr()), DEVICE)
+            return out[:self.N]
+        out = np.zeros(max(self.N, 1), np.float64)
+        self.call("csmp_colnorms", ptr(out), HOST)
+        return out[:self.N]
+
+    def cumbabel(self, k, normalize=False):
+        """csmp_cumbabel: (mu, pair) -- mu[m-1] = mu_1(m) for m = 1..k, and the 0-based columns (i, j), i < j, that attain mu_1(1)."""
+        k = int(k)
+        mu = np.zeros(max(k, 1), np.float64)
+        pair = np.full(2, -1, np.int64)
+        self.call("csmp_cumbabel", i64(k), int(normalize), ptr(mu), ptr(pair))
+        return mu[:k], (int(pair[0]), int(pair[1]))
 
     # ---- primitives
     def sweep(self, r, topk=1, want_abs=True):

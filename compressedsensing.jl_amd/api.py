@@ -16,6 +16,7 @@ Same names, argument meaning and error behaviour as the reference (paths relativ
     MP / OMP / GOMP functors with update!    src/matchingpursuit.jl:10-31,44-70,95-123
     argmaxinner!(P[, k])                     src/matchingpursuit.jl:181-193
     ista(A, b, λ | w[, x]; maxiter, stepsize) / fista(...) / shrinkage(x, α)   src/basispursuit.jl:144,164-204
+    colnorms(A) / coherence(A) / babel(A, k) / cumbabel(A, k)               src/util.jl:2,96-115
 
 `A` is either a numpy matrix (uploaded to HBM for the duration of the call) or a `Dictionary`
 (uploaded once, resident -- what a caller looping over many signals wants).  Results are
@@ -182,6 +183,50 @@ def fista(A, b, lam_or_w, x=None, *, maxiter=1024, stepsize=1e-2):
     """fista(A,b,λ | w,x; maxiter, stepsize): Beck-Teboulle acceleration of ista on the same objective -- t₁ = 1,
     t⁺ = (1 + √(1 + 4t²))/2, y⁺ = x⁺ + ((t - 1)/t⁺)(x⁺ - x).  The reference's own fista (:186-204) does not run."""
     return _ista(A, b, lam_or_w, x, maxiter, stepsize, True)
+
+
+# ------------------------------------------------------------------------------------ dictionary analysis
+def colnorms(A):
+    """colnorms(A) = [norm(a) for a in eachcol(A)] (src/util.jl:2), Float64."""
+    D, tmp = _dict(A)
+    try:
+        return D.ctx.colnorms()
+    finally:
+        if tmp:
+            D.close()
+
+
+def _cumbabel(A, k, normalize):
+    _, N, _ = _meta(A)
+    if not _is_int(k) or not 1 <= k <= min(N, _lib.BABEL_KMAX):
+        raise ValueError(f"k = {k} has to lie in 1 .. min(size(A, 2), {_lib.BABEL_KMAX}) = {min(N, _lib.BABEL_KMAX)}")
+    if normalize not in (False, True, 0, 1):
+        raise ValueError(f"normalize = {normalize} has to be False or True")
+    D, tmp = _dict(A)
+    try:
+        return D.ctx.cumbabel(int(k), bool(normalize))
+    finally:
+        if tmp:
+            D.close()
+
+
+def cumbabel(A, k, normalize=False):
+    """cumbabel(A, k): the Babel function μ₁(1..k) (src/util.jl:103-115) -- for every column the k largest |⟨a_i, a_j⟩|, j ≠ i, in
+    descending order, their running sums, the maximum over the columns.  The inner products are raw, as in the reference (which
+    assumes unit-norm columns); normalize=True divides each by ‖a_i‖ ‖a_j‖ (a zero column contributes 0).  k ≤ min(N, 1024)."""
+    return _cumbabel(A, k, normalize)[0]
+
+
+def babel(A, k, normalize=False):
+    """babel(A, k) = cumbabel(A, k)[k] (src/util.jl:99)."""
+    return float(_cumbabel(A, k, normalize)[0][-1])
+
+
+def coherence(A, normalize=False, return_pair=False):
+    """coherence(A) = babel(A, 1) (src/util.jl:96), the mutual coherence.  return_pair=True: (μ, (i, j)) with the 0-based columns
+    i < j that attain it (the lowest i, then the lowest j among equals; (-1, -1) for a single column)."""
+    mu, pair = _cumbabel(A, 1, normalize)
+    return (float(mu[0]), pair) if return_pair else float(mu[0])
 
 
 def sp(A, b, k, delta=1e-12, maxiter=None):

@@ -17,6 +17,7 @@
 #include "csmp_gram.hpp"
 #include "csmp_swap.hpp"
 #include "csmp_ista.hpp"
+#include "csmp_analysis.hpp"
 
 #include <algorithm>
 #include <iterator>
@@ -52,5 +53,6 @@ using namespace csmp;
 #include "host/batched.hpp"
 #include "host/screened.hpp"
 #include "host/ista.hpp"
+#include "host/analysis.hpp"
 #include "host/measure.hpp"
 #include "host/rccl.hpp"

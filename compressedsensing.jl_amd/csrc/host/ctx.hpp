@@ -143,6 +143,15 @@ struct IstaBuf {
     int Mv = 0, P = 0;        // ... and the column length and workgroup count of the partials
 };
 
+// dictionary analysis (csmp_analysis.hpp, host/analysis.hpp): the column norms (or their reciprocals), one 128 x N strip of |A'A|, the
+// strip's per-row results and the call's running results, made on first use, sized by the dictionary
+struct AnalysisBuf {
+    double *norms = nullptr, *strip = nullptr, *rowcum = nullptr, *rowtop = nullptr, *mu = nullptr;
+    long long* rowarg = nullptr;
+    BabelBest* best = nullptr;
+    int64_t N = 0;  // atoms the buffers were made for (0: none)
+};
+
 struct csmp_ctx;
 // Subspace Pursuit as a resumable job: see host/gomp_sp.hpp
 struct SpJob {
@@ -246,6 +255,7 @@ struct csmp_ctx {
     bool tick_sweep_first = false;  // dispatch the sweep workgroups ahead of the append stages (CSMP_TICK_ORDER=1)
     Batch bt;
     IstaBuf ista;
+    AnalysisBuf analysis;
     // profiling
     bool prof = false;
     int prof_every = 1;       // time every n-th sweep launch only (an event pair costs a few us of stream time)

@@ -86,6 +86,11 @@ static void ista_free(IstaBuf& t) {
     t = IstaBuf();
 }
 
+static void analysis_free(AnalysisBuf& t) {
+    dfree(t.norms); dfree(t.strip); dfree(t.rowcum); dfree(t.rowtop); dfree(t.mu); dfree(t.rowarg); dfree(t.best);
+    t = AnalysisBuf();
+}
+
 static void dict_release(csmp_ctx* ctx) {
     if (ctx->share && --ctx->share->refs == 0) {
         if (ctx->share->kind == 0) (void)hipFree(ctx->share->p);
@@ -109,6 +114,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     }
     batch_free(ctx->bt, false);
     ista_free(ctx->ista);
+    analysis_free(ctx->analysis);
     if (ctx->comm) (void)csmp_comm_free(ctx);
     for (auto& t : ctx->twins) {
         if (t) (void)csmp_destroy(t);

@@ -184,6 +184,32 @@ fista(A::MatOrDict, b::AbstractVector, w::AbstractVector, x::AbstractVector = sp
 fista(A::MatOrDict, b::AbstractVector, λ::Real, x::AbstractVector = spzeros(size(A, 2)); maxiter::Int = 1024, stepsize::Real = 1e-2) =
     ista_call(A, b, Float64[λ], x, maxiter, stepsize, true)
 
+# ---------------------------------------------------------------------------------- dictionary analysis
+# src/util.jl:2,96-115: colnorms, coherence, babel, cumbabel.  The inner products are raw, as in the reference (which assumes unit-norm
+# columns); normalize = true divides each by ‖a_i‖ ‖a_j‖.  cumbabel_pair also returns the columns (i, j), i < j, 1-based, that attain
+# μ₁(1) (the lowest i, then the lowest j among equals; (0, 0) for a single column).
+const CSMP_BABEL_KMAX = 1024
+function colnorms(A::MatOrDict)
+    D = dict(A)
+    out = zeros(Float64, size(D, 2))
+    GC.@preserve out check(D, ccall((:csmp_colnorms, libcsmp), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint), D.ctx, out, CSMP_HOST))
+    return out
+end
+function cumbabel_pair(A::MatOrDict, k::Integer; normalize::Bool = false)
+    D = dict(A)
+    1 ≤ k ≤ min(size(D, 2), CSMP_BABEL_KMAX) || throw("k = $k has to lie in 1 .. min(size(A, 2), $CSMP_BABEL_KMAX)")
+    μ₁, pair = zeros(Float64, k), zeros(Int64, 2)
+    GC.@preserve μ₁ pair check(D, ccall((:csmp_cumbabel, libcsmp), Cint, (Ptr{Cvoid}, Int64, Cint, Ptr{Cdouble}, Ptr{Int64}),
+        D.ctx, k, Cint(normalize), μ₁, pair))
+    return μ₁, (Int(pair[1]) + 1, Int(pair[2]) + 1)
+end
+cumbabel(A::MatOrDict, k::Integer; normalize::Bool = false) = cumbabel_pair(A, k; normalize = normalize)[1]
+babel(A::MatOrDict, k::Integer; normalize::Bool = false) = cumbabel(A, k; normalize = normalize)[k]
+function coherence(A::MatOrDict; normalize::Bool = false, return_pair::Bool = false)
+    μ₁, pair = cumbabel_pair(A, 1; normalize = normalize)
+    return return_pair ? (μ₁[1], pair) : μ₁[1]
+end
+
 # ---------------------------------------------------------------------------------- sp
 # src/twostage.jl:87-101
 function sp(A::MatOrDict{T}, b::AbstractVector, k::Int, δ::Real = 1e-12; maxiter = 16k) where {T}

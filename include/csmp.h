@@ -392,6 +392,33 @@ int csmp_ista(csmp_ctx *ctx, const void *b, int b_dtype, const double *w, int64_
               int64_t maxiter, double stepsize, int accel,
               double *x, int x_loc, double *resnorm);
 
+/* ------------------------------------------------------------------ dictionary analysis
+ * colnorms(A): src/util.jl:2.  norms[j] = ||a_j||_2 of every column of the resident dictionary, N doubles, to host memory
+ * (out_loc = CSMP_HOST) or device memory (CSMP_DEVICE; the call still returns with the work done).  Float64 on the exactly
+ * promoted dictionary values; a zero column gives 0.
+ * CSMP_EINVAL: a null ctx or norms, an out_loc that is neither.  CSMP_ESTATE: no dictionary -- and a host-streamed dictionary
+ * (CSMP_HOST_STREAMED), which the analysis entries do not serve.  CSMP_ENOMEM: the N doubles could not be allocated; nothing
+ * is left behind. */
+int csmp_colnorms(csmp_ctx *ctx, double *norms, int out_loc);              /* N doubles, CSMP_HOST or CSMP_DEVICE */
+
+/* coherence(A) / babel(A,k) / cumbabel(A,k): src/util.jl:96-115.  mu[m-1] = mu_1(m), m = 1..k, the Babel function: for every
+ * column i form g = |A' a_i| and set g[i] = 0 -- the self entry does not count, and it stays in the vector as a zero, so with
+ * k = N the last term added is that zero --, sort the k largest entries of g in descending order, take their running sums
+ * s_i(1..k); mu_1(m) = max_i s_i(m).  babel(A,k) = mu[k-1], coherence(A) = mu[0].  The inner products are raw, as in the
+ * reference, which assumes unit-norm columns and does not divide.
+ * normalize = 1 (an addition): every entry is |<a_i, a_j>| / (||a_i|| ||a_j||), the coherence of a dictionary that has not been
+ * normalised; a zero column contributes 0.  normalize = 0: the reference's values.
+ * pair (may be NULL; an addition): the two columns (i, j), i < j, 0-based, that attain mu_1(1); among equal values the lowest i
+ * wins, then the lowest j (tie-break); (-1, -1) when N = 1.  mu and pair are host arrays of k doubles and 2 int64.
+ * Float64 on the exactly promoted dictionary values, every sum in a fixed order: the same call returns the same bits every time.
+ * The N x N Gram matrix is never held: the device keeps one strip of 128 rows of it (1 KiB per column of the dictionary).
+ * CSMP_EINVAL: a null ctx or mu, a normalize that is neither 0 nor 1.  CSMP_ERANGE: k < 1 or k > min(N, CSMP_BABEL_KMAX).
+ * CSMP_ESTATE: no dictionary -- and a host-streamed dictionary (CSMP_HOST_STREAMED): the call is N passes over the dictionary,
+ * which would cross the host link each time (as csmp_ista).  CSMP_ENOMEM: a buffer could not be allocated; nothing is left
+ * behind, and the next call starts afresh. */
+#define CSMP_BABEL_KMAX 1024
+int csmp_cumbabel(csmp_ctx *ctx, int64_t k, int normalize, double *mu, int64_t *pair);  /* mu: k doubles (host); pair: 2 int64 (host) or NULL */
+
 /* ------------------------------------------------------------------ primitives
  * argmaxinner!(P) / argmaxinner!(P,k): src/matchingpursuit.jl:181-193.  r: length-M Float64
  * host vector.  abs_corr (may be NULL): receives |A' r| (length N).  top_idx/top_val: the
