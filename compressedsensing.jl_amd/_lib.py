@@ -82,6 +82,9 @@ SIGNATURES = {
     "csmp_solver_remove": (C.c_int, [vp, i64]),
     "csmp_solver_state": (C.c_int, [vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp, C.POINTER(C.c_int)]),
     "csmp_ista": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, i64, i64, C.c_double, C.c_int, vp, C.c_int, C.POINTER(C.c_double)]),
+    "csmp_ard_weights": (C.c_int, [vp, vp, vp, C.c_double, i64, vp, C.c_int]),
+    "csmp_ista_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, i64, i64, C.c_double, i64, C.c_double, C.c_int, vp, C.c_int, vp,
+                                       C.POINTER(i64), C.POINTER(C.c_double)]),
     "csmp_colnorms": (C.c_int, [vp, vp, C.c_int]),
     "csmp_cumbabel": (C.c_int, [vp, i64, C.c_int, vp, vp]),
     "csmp_sweep": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -94,6 +97,7 @@ INTERNAL_SIGNATURES = {
     "csmp_profile_enable": (C.c_int, [vp, C.c_int]),
     "csmp_profile_read": (C.c_int, [vp, C.POINTER(i64), C.POINTER(C.c_double), C.c_int]),
     "csmp_bench_sweep": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "csmp_bench_ard_forms": (C.c_int, [vp, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "csmp_profile_overhead": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
     "csmp_live_resources": (C.c_int, [C.POINTER(i64)] * 6),
     "csmp_profile_window": (C.c_int, [vp, C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
@@ -108,6 +112,8 @@ TUNE = {"sweep_grid": 2, "sweep_unit": 3, "tick_grid": 4, "batch_budget_mib": 5,
 
 COMM_ID_BYTES = 128  # CSMP_COMM_ID_BYTES
 BABEL_KMAX = 1024  # CSMP_BABEL_KMAX
+ARD_KMAX = 1024  # CSMP_ARD_KMAX
+REWEIGHT_CANDES, REWEIGHT_ARD = 0, 1  # CSMP_REWEIGHT_*
 
 
 def live_resources():
@@ -187,6 +193,10 @@ def dtype_code(dt):
     if dt == np.float64:
         return F64
     raise TypeError(f"unsupported element type {dt}: the dictionary and b must be float32 or float64")
+
+
+def _scheme(scheme):
+    return {"candes": REWEIGHT_CANDES, "ard": REWEIGHT_ARD}.get(scheme, scheme)
 
 
 class Context:
@@ -670,6 +680,54 @@ class Context:
                   i64(len(idx0)), i64(int(maxiter)), C.c_double(stepsize), int(bool(accel)), vp(x.data_ptr()), DEVICE, C.byref(rn))
         return rn.value
 
+    # ---- reweighted l1
+    def ard_weights(self, x, w=None, eps=1e-2, iter=8):
+        """csmp_ard_weights on host vectors: the N weights after `iter` iterations of ard_weights! from w (None: ones)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        w = np.ones(self.N) if w is None else np.ascontiguousarray(w, dtype=np.float64)
+        if x.shape != (self.N,) or w.shape != (self.N,):
+            raise CsmpError(EDIM, "length(x) and length(w) have to be size(A, 2)")
+        out = np.zeros(max(self.N, 1), np.float64)
+        self.call("csmp_ard_weights", ptr(x), ptr(w), C.c_double(eps), i64(int(iter)), ptr(out), HOST)
+        return out[:self.N]
+
+    def ard_weights_device(self, x, w, out, eps=1e-2, iter=8):
+        """torch CUDA float64 vectors of length N: x, the weights w to start from, out (may be w) receives the result."""
+        import torch
+        for v in (x, w, out):
+            if not (v.is_cuda and v.is_contiguous() and v.shape == (self.N,) and v.dtype == torch.float64):
+                raise CsmpError(EDIM, "x, w and out must be contiguous CUDA float64 vectors of length size(A, 2)")
+        self.call("csmp_ard_weights", vp(x.data_ptr()), vp(w.data_ptr()), C.c_double(eps), i64(int(iter)), vp(out.data_ptr()), DEVICE)
+
+    def ista_reweighted(self, b, lam, scheme, eps=1e-2, ard_iter=8, outer_maxiter=8, min_decrease=1e-8, maxiter=1024, stepsize=1e-2, accel=False,
+                        return_weights=False):
+        """csmp_ista_reweighted on a host signal: (dense x, ||b - A x||, solves done[, the last weights]).  scheme: "candes" / "ard"."""
+        b = self._b(b)
+        x = np.zeros(max(self.N, 1), np.float64)
+        w = np.zeros(max(self.N, 1), np.float64) if return_weights else None
+        rn, done = C.c_double(0), i64(0)
+        self.call("csmp_ista_reweighted", ptr(b), dtype_code(b.dtype), C.c_double(lam), _scheme(scheme), C.c_double(eps), i64(int(ard_iter)),
+                  i64(int(outer_maxiter)), C.c_double(min_decrease), i64(int(maxiter)), C.c_double(stepsize), int(bool(accel)), ptr(x), HOST, ptr(w),
+                  C.byref(done), C.byref(rn))
+        res = (x[:self.N], rn.value, int(done.value))
+        return res + (w[:self.N],) if return_weights else res
+
+    def ista_reweighted_device(self, b, lam, scheme, x, w=None, eps=1e-2, ard_iter=8, outer_maxiter=8, min_decrease=1e-8, maxiter=1024,
+                               stepsize=1e-2, accel=False):
+        """torch CUDA tensors: b (M,) float32 / float64; x and (optionally) w (N,) float64 receive the result and the last weights.
+        Returns (||b - A x||, solves done); the work is done when the call returns."""
+        import torch
+        if not (b.is_cuda and b.is_contiguous() and b.shape == (self.M,) and b.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "b must be a contiguous CUDA vector of length size(A, 1), float32 or float64")
+        for v in (x,) if w is None else (x, w):
+            if not (v.is_cuda and v.is_contiguous() and v.shape == (self.N,) and v.dtype == torch.float64):
+                raise CsmpError(EDIM, "x and w must be contiguous CUDA float64 vectors of length size(A, 2)")
+        rn, done = C.c_double(0), i64(0)
+        self.call("csmp_ista_reweighted", vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64, C.c_double(lam), _scheme(scheme),
+                  C.c_double(eps), i64(int(ard_iter)), i64(int(outer_maxiter)), C.c_double(min_decrease), i64(int(maxiter)), C.c_double(stepsize),
+                  int(bool(accel)), vp(x.data_ptr()), DEVICE, vp(w.data_ptr() if w is not None else 0), C.byref(done), C.byref(rn))
+        return rn.value, int(done.value)
+
     # ---- dictionary analysis
     def colnorms(self, device=False):
         """csmp_colnorms: ||a_j|| of every column, Float64[N] -- a numpy array, or (device=True) a torch CUDA tensor."""
@@ -735,6 +793,12 @@ class Context:
         ms = C.c_double(0)
         self.call("csmp_bench_sweep", int(variant), int(reps), C.byref(ms))
         return ms.value
+
+    def bench_ard_forms(self, variant, reps, eps=1e-2):
+        """csmp_bench_ard_forms (csmp_internal.h): (average ms of the N-pass, max |w fused - w split|) on the last ard_weights call's directions"""
+        ms, diff = C.c_double(0), C.c_double(0)
+        self.call("csmp_bench_ard_forms", int(variant), int(reps), C.c_double(eps), C.byref(ms), C.byref(diff))
+        return ms.value, diff.value
 
     def sweep_config(self):
         """what configure_sweep chose for the resident dictionary (csmp_internal.h)"""

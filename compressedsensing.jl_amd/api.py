@@ -185,6 +185,83 @@ def fista(A, b, lam_or_w, x=None, *, maxiter=1024, stepsize=1e-2):
     return _ista(A, b, lam_or_w, x, maxiter, stepsize, True)
 
 
+# ------------------------------------------------------------------------------------ reweighted l1
+def candes_weights(x, eps=1e-2):
+    """candes_weights!(w, x, ε): w_j = 1 / (|x_j| + ε) (src/basispursuit.jl:33-39), Float64[N]; x a vector or a SparseVector.  NaN or Inf
+    in the result is an error, as in the reference."""
+    if not (eps > 0 and np.isfinite(eps)):
+        raise ValueError(f"eps = {eps} has to be positive and finite")
+    x = x.to_dense() if isinstance(x, SparseVector) else np.asarray(x, dtype=np.float64)
+    w = 1.0 / (np.abs(x) + eps)
+    if not np.all(np.isfinite(w)):
+        raise ValueError("weights contain NaN or Inf")
+    return w
+
+
+def ard_weights(A, x, w=None, eps=1e-2, iter=8):
+    """ard_weights!(w, A, x, ε, iter) (src/basispursuit.jl:49-65): iter times over, d = |x| ./ w, K = εI + A diag(d) Aᵀ,
+    w_j = √max(a_jᵀ K⁻¹ a_j, 0).  Returns the new weights, Float64[N]; w (default: ones) is not changed.  A zero weight is an error
+    ("weights cannot be zero"); nnz(x) ≤ min(size(A, 1), 1024)."""
+    M, N, _ = _meta(A)
+    if not (eps > 0 and np.isfinite(eps)):
+        raise ValueError(f"eps = {eps} has to be positive and finite")
+    if not _is_int(iter) or iter < 1:
+        raise ValueError(f"iter = {iter} has to be at least 1")
+    x = x.to_dense() if isinstance(x, SparseVector) else np.asarray(x, dtype=np.float64)
+    w = np.ones(N) if w is None else np.asarray(w, dtype=np.float64)
+    if x.shape != (N,) or w.shape != (N,):
+        raise ValueError(f"length(x) = {x.shape}, length(w) = {w.shape} but size(A, 2) = {N}")
+    if np.any(w == 0):
+        raise ValueError("weights cannot be zero")
+    D, tmp = _dict(A)
+    try:
+        return D.ctx.ard_weights(x, w, float(eps), int(iter))
+    finally:
+        if tmp:
+            D.close()
+
+
+def _ista_reweighted(A, b, lam, scheme, eps, maxiter, min_decrease, inner_maxiter, stepsize, accel, return_weights, ard_iter=8):
+    M, N, _ = _meta(A)
+    if not (lam >= 0 and np.isfinite(lam)):
+        raise ValueError(f"lam = {lam} has to be non-negative and finite")
+    if not (eps > 0 and np.isfinite(eps)):
+        raise ValueError(f"eps = {eps} has to be positive and finite")
+    if not _is_int(maxiter) or maxiter < 1:
+        raise ValueError(f"maxiter = {maxiter} has to be at least 1")
+    if not min_decrease >= 0:
+        raise ValueError(f"min_decrease = {min_decrease} has to be non-negative")
+    if not inner_maxiter >= 0:
+        raise ValueError(f"inner_maxiter = {inner_maxiter} has to be non-negative")
+    if not (stepsize > 0 and np.isfinite(stepsize)):
+        raise ValueError(f"stepsize = {stepsize} has to be positive and finite")
+    D, tmp = _dict(A)
+    try:
+        out = D.ctx.ista_reweighted(b, float(lam), scheme, float(eps), ard_iter, int(maxiter), float(min_decrease), int(inner_maxiter),
+                                    float(stepsize), accel, return_weights)
+        nz = np.flatnonzero(out[0])
+        x = SparseVector(N, nz, out[0][nz])
+        return (x, out[3]) if return_weights else x
+    finally:
+        if tmp:
+            D.close()
+
+
+def ista_candes(A, b, lam, eps=1e-2, *, maxiter=8, min_decrease=1e-8, inner_maxiter=1024, stepsize=1e-2, accel=False, return_weights=False):
+    """candes_reweighting (bp_candes, src/basispursuit.jl:18-45) with ista (accel=True: fista) as the solver of
+    ‖b - A x‖² + λ Σ w_j |x_j|: x = solve(w = 1); up to maxiter - 1 times w_j = 1 / (|x_j| + ε), xs = solve(w) warm-started from x,
+    stop once ‖xs - x‖ < min_decrease.  return_weights=True: (x, the last w)."""
+    return _ista_reweighted(A, b, lam, "candes", eps, maxiter, min_decrease, inner_maxiter, stepsize, accel, return_weights)
+
+
+def ista_ard(A, b, lam, eps=1e-2, *, maxiter=8, min_decrease=1e-8, inner_maxiter=1024, stepsize=1e-2, accel=False, return_weights=False, iter=8):
+    """ard_reweighting (bp_ard, src/basispursuit.jl:18-31,49-74) with ista / fista as the solver: as ista_candes with
+    ard_weights!(w, A, x, ε, iter) on the weights of the previous outer iteration (from ones)."""
+    if not _is_int(iter) or iter < 1:
+        raise ValueError(f"iter = {iter} has to be at least 1")
+    return _ista_reweighted(A, b, lam, "ard", eps, maxiter, min_decrease, inner_maxiter, stepsize, accel, return_weights, int(iter))
+
+
 # ------------------------------------------------------------------------------------ dictionary analysis
 def colnorms(A):
     """colnorms(A) = [norm(a) for a in eachcol(A)] (src/util.jl:2), Float64."""

@@ -18,6 +18,7 @@
 #include "csmp_swap.hpp"
 #include "csmp_ista.hpp"
 #include "csmp_analysis.hpp"
+#include "csmp_reweight.hpp"
 
 #include <algorithm>
 #include <iterator>
@@ -54,5 +55,6 @@ using namespace csmp;
 #include "host/screened.hpp"
 #include "host/ista.hpp"
 #include "host/analysis.hpp"
+#include "host/reweight.hpp"
 #include "host/measure.hpp"
 #include "host/rccl.hpp"

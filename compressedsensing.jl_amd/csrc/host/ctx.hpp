@@ -152,6 +152,20 @@ struct AnalysisBuf {
     int64_t N = 0;  // atoms the buffers were made for (0: none)
 };
 
+// reweighted l1 (csmp_reweight.hpp, host/reweight.hpp): the weights and the previous iterate (sized by the dictionary), and the support
+// factor of ard_weights! (sized by the support, rounded up to whole 64-column tiles: np), made on first use
+struct RwBuf {
+    double *w = nullptr, *xprev = nullptr, *xin = nullptr, *npart = nullptr, *zeroM = nullptr;
+    int* cols = nullptr;
+    RwInfo* info = nullptr;
+    DevState* st = nullptr;
+    int64_t N = 0;  // atoms the buffers above were made for (0: none)
+    double *xS = nullptr, *wS = nullptr, *Gs = nullptr, *Y = nullptr, *Gm = nullptr, *Gpart = nullptr, *gdiag = nullptr, *Dfac = nullptr,
+           *rhs_part = nullptr, *W = nullptr;
+    char* Acomp = nullptr;
+    int np = 0, nsplit = 0;  // columns the support's buffers were made for (0: none), and k_gram's row slices
+};
+
 struct csmp_ctx;
 // Subspace Pursuit as a resumable job: see host/gomp_sp.hpp
 struct SpJob {
@@ -256,6 +270,7 @@ struct csmp_ctx {
     Batch bt;
     IstaBuf ista;
     AnalysisBuf analysis;
+    RwBuf rw;
     // profiling
     bool prof = false;
     int prof_every = 1;       // time every n-th sweep launch only (an event pair costs a few us of stream time)

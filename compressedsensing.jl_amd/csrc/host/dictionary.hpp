@@ -246,6 +246,7 @@ static int dict_forget(csmp_ctx* ctx) {
     batch_free(ctx->bt, false);
     ista_free(ctx->ista);
     analysis_free(ctx->analysis);
+    rw_free(ctx->rw);
     return CSMP_OK;
 }
 

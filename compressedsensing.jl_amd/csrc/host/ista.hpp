@@ -73,6 +73,23 @@ static int ista_launch_residual(csmp_ctx* ctx) {
 }
 static int ista_residual(csmp_ctx* ctx) { return ctx->dtype == CSMP_F32 ? ista_launch_residual<float>(ctx) : ista_launch_residual<double>(ctx); }
 
+// exactly maxiter iterations from the x, y and weights in the context's buffers, no stopping rule (:177); nothing here waits for the
+// device.  listed: the list (and r) belong to the current y -- false on entry only for x = y = 0, where r = b already.
+static int ista_iterate(csmp_ctx* ctx, int64_t nw, int64_t maxiter, double stepsize, int accel, bool& listed) {
+    Solver& s = ctx->s;
+    double tk = 1.0;
+    for (int64_t it = 1; it <= maxiter; ++it) {
+        if (listed) CHECK(ista_residual(ctx));  // (the first iteration from x = 0: r = b already)
+        CHECK(launch_sweep(ctx, s.r, 0.0, 0, 0));
+        const double tn = (1.0 + std::sqrt(1.0 + 4.0 * tk * tk)) / 2.0;
+        const double beta = accel ? (tk - 1.0) / tn : 0.0;
+        tk = tn;
+        CHECK(ista_launch_update(ctx, nw, stepsize, beta, (accel ? ISTA_ACCEL : 0) | (it == maxiter ? ISTA_LIST_X : 0)));
+        listed = true;
+    }
+    return CSMP_OK;
+}
+
 extern "C" int csmp_ista(csmp_ctx* ctx, const void* b, int b_dtype, const double* w, int64_t nw, const int64_t* idx0, const double* val0,
                          int64_t nnz0, int64_t maxiter, double stepsize, int accel, double* x, int x_loc, double* resnorm) {
     if (!ctx) return CSMP_EINVAL;
@@ -122,17 +139,7 @@ extern "C" int csmp_ista(csmp_ctx* ctx, const void* b, int b_dtype, const double
         HIPCHECK(hipMemsetAsync(t.x, 0, (size_t)ctx->N * sizeof(double), ctx->stream));
         HIPCHECK(hipMemsetAsync(t.y, 0, (size_t)ctx->N * sizeof(double), ctx->stream));
     }
-    // exactly maxiter iterations, no stopping rule (:177); nothing below waits for the device
-    double tk = 1.0;
-    for (int64_t it = 1; it <= maxiter; ++it) {
-        if (listed) CHECK(ista_residual(ctx));  // (the first iteration from x = 0: r = b already)
-        CHECK(launch_sweep(ctx, s.r, 0.0, 0, 0));
-        const double tn = (1.0 + std::sqrt(1.0 + 4.0 * tk * tk)) / 2.0;
-        const double beta = accel ? (tk - 1.0) / tn : 0.0;
-        tk = tn;
-        CHECK(ista_launch_update(ctx, nw, stepsize, beta, (accel ? ISTA_ACCEL : 0) | (it == maxiter ? ISTA_LIST_X : 0)));
-        listed = true;
-    }
+    CHECK(ista_iterate(ctx, nw, maxiter, stepsize, accel, listed));
     if (resnorm) {
         if (listed) CHECK(ista_residual(ctx));
         CHECK(residual_norm(ctx, resnorm));

@@ -91,6 +91,17 @@ static void analysis_free(AnalysisBuf& t) {
     t = AnalysisBuf();
 }
 
+static void rw_free_support(RwBuf& t) {
+    dfree(t.xS); dfree(t.wS); dfree(t.Gs); dfree(t.Y); dfree(t.Gm); dfree(t.Gpart); dfree(t.gdiag); dfree(t.Dfac); dfree(t.rhs_part); dfree(t.W);
+    dfree(t.Acomp);
+    t.np = t.nsplit = 0;
+}
+static void rw_free(RwBuf& t) {
+    rw_free_support(t);
+    dfree(t.w); dfree(t.xprev); dfree(t.xin); dfree(t.npart); dfree(t.zeroM); dfree(t.cols); dfree(t.info); dfree(t.st);
+    t = RwBuf();
+}
+
 static void dict_release(csmp_ctx* ctx) {
     if (ctx->share && --ctx->share->refs == 0) {
         if (ctx->share->kind == 0) (void)hipFree(ctx->share->p);
@@ -115,6 +126,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     batch_free(ctx->bt, false);
     ista_free(ctx->ista);
     analysis_free(ctx->analysis);
+    rw_free(ctx->rw);
     if (ctx->comm) (void)csmp_comm_free(ctx);
     for (auto& t : ctx->twins) {
         if (t) (void)csmp_destroy(t);

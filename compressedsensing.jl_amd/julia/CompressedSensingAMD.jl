@@ -184,6 +184,49 @@ fista(A::MatOrDict, b::AbstractVector, w::AbstractVector, x::AbstractVector = sp
 fista(A::MatOrDict, b::AbstractVector, λ::Real, x::AbstractVector = spzeros(size(A, 2)); maxiter::Int = 1024, stepsize::Real = 1e-2) =
     ista_call(A, b, Float64[λ], x, maxiter, stepsize, true)
 
+# ---------------------------------------------------------------------------------- reweighted l1
+# src/basispursuit.jl:18-74: candes_weights!, ard_weights! and basispursuit_reweighting with ista / fista as the solver of
+# ‖b - A x‖² + λ Σ w_j |x_j| (the reference's bp / bpd need an LP / SOCP solver and are not part of libcsmp).
+const CSMP_ARD_KMAX = 1024
+const CSMP_REWEIGHT_CANDES = 0
+const CSMP_REWEIGHT_ARD = 1
+candes_weight(x, ε) = inv(abs(x) + ε)
+function candes_weights!(w::AbstractVector, x::AbstractVector, ε::Real)
+    ε > 0 || throw("ε = $ε has to be positive")
+    @. w = candes_weight(x, ε)
+    if any(isnan, w) || any(isinf, w)
+        throw("weights contain NaN or Inf: $w")
+    end
+    return w
+end
+function ard_weights!(w::Vector{Float64}, A::MatOrDict, x::AbstractVector, ε::Real, iter::Int = 8)
+    any(==(0), w) && error("weights cannot be zero")
+    D = dict(A)
+    xd = convert(Vector{Float64}, Vector(x))
+    GC.@preserve xd w check(D, ccall((:csmp_ard_weights, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Int64, Ptr{Cdouble}, Cint),
+        D.ctx, xd, w, ε, iter, w, CSMP_HOST))
+    return w
+end
+function ista_reweighted(A::MatOrDict, b::AbstractVector, λ::Real, scheme::Integer, ε::Real, ard_iter::Int, maxiter::Int, min_decrease::Real,
+                         inner_maxiter::Int, stepsize::Real, accel::Bool, return_weights::Bool)
+    D = dict(A)
+    bb, bt = bvec(b)
+    xd, w = zeros(Float64, size(D, 2)), zeros(Float64, size(D, 2))
+    done, rn = Ref{Int64}(0), Ref{Cdouble}(0)
+    GC.@preserve bb xd w check(D, ccall((:csmp_ista_reweighted, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cint, Cdouble, Int64, Int64, Cdouble, Int64, Cdouble, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble},
+         Ref{Int64}, Ref{Cdouble}),
+        D.ctx, bb, bt, λ, Cint(scheme), ε, ard_iter, maxiter, min_decrease, inner_maxiter, stepsize, Cint(accel), xd, CSMP_HOST, w, done, rn))
+    return return_weights ? (sparse(xd), w) : sparse(xd)
+end
+ista_candes(A::MatOrDict, b::AbstractVector, λ::Real, ε::Real = 1e-2; maxiter::Int = 8, min_decrease::Real = 1e-8, inner_maxiter::Int = 1024,
+            stepsize::Real = 1e-2, accel::Bool = false, return_weights::Bool = false) =
+    ista_reweighted(A, b, λ, CSMP_REWEIGHT_CANDES, ε, 8, maxiter, min_decrease, inner_maxiter, stepsize, accel, return_weights)
+ista_ard(A::MatOrDict, b::AbstractVector, λ::Real, ε::Real = 1e-2; maxiter::Int = 8, min_decrease::Real = 1e-8, inner_maxiter::Int = 1024,
+         stepsize::Real = 1e-2, accel::Bool = false, return_weights::Bool = false, iter::Int = 8) =
+    ista_reweighted(A, b, λ, CSMP_REWEIGHT_ARD, ε, iter, maxiter, min_decrease, inner_maxiter, stepsize, accel, return_weights)
+
 # ---------------------------------------------------------------------------------- dictionary analysis
 # src/util.jl:2,96-115: colnorms, coherence, babel, cumbabel.  The inner products are raw, as in the reference (which assumes unit-norm
 # columns); normalize = true divides each by ‖a_i‖ ‖a_j‖.  cumbabel_pair also returns the columns (i, j), i < j, 1-based, that attain

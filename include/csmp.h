@@ -392,6 +392,42 @@ int csmp_ista(csmp_ctx *ctx, const void *b, int b_dtype, const double *w, int64_
               int64_t maxiter, double stepsize, int accel,
               double *x, int x_loc, double *resnorm);
 
+/* ------------------------------------------------------------------ reweighted l1
+ * candes_weights! / ard_weights! / basispursuit_reweighting: src/basispursuit.jl:18-74 (bp_candes, bp_ard; bpd_candes, bpd_ard :102-124),
+ * with ista / fista as the inner solver -- the reference's bp / bpd need an LP / SOCP solver and are not part of this library.
+ *
+ * ard_weights!(w, A, x, eps, iter) (:49-65): `iter` times over,  d = |x| ./ w;  K = eps I + A diag(d) A';
+ * w_j = sqrt(max(a_j' K^-1 a_j, 0)) for every atom.  x, w_in, w_out: N doubles each, all three in host memory (loc = CSMP_HOST) or all
+ * three in device memory (CSMP_DEVICE; the call still returns with the work done); w_out may be w_in.  Only the support S of x
+ * enters K: with k = |S|, G = A_S'A_S and L L' = eps diag(w_S ./ |x_S|) + G,  a_j' K^-1 a_j = (|a_j|^2 - |L^-1 A_S' a_j|^2) / eps;
+ * k = 0 gives w_j = |a_j| / sqrt(eps).  Float64 on the exactly promoted dictionary values, every sum in a fixed order: the same call
+ * returns the same bits every time.
+ * CSMP_EINVAL: a null pointer, eps that is not positive and finite, iter < 1, a weight that is zero (the reference: "weights cannot
+ * be zero", :50-52), negative or not finite, an x that is not finite.  CSMP_ERANGE: nnz(x) > min(M, CSMP_ARD_KMAX) -- a basic
+ * solution of bp has at most M non-zeros.  CSMP_ESTATE: no dictionary, or a host-streamed one (as csmp_ista).  CSMP_ENOMEM: a buffer
+ * could not be allocated; nothing of it is left behind, and the next call starts afresh. */
+#define CSMP_ARD_KMAX 1024
+int csmp_ard_weights(csmp_ctx *ctx, const double *x, const double *w_in, double eps, int64_t iter, double *w_out, int loc);
+
+/* basispursuit_reweighting (:18-31) on  ||b - A x||^2 + lambda sum_j w_j |x_j|:  x = solve(w = 1);  then for i = 2 .. outer_maxiter:
+ * w from x -- scheme CSMP_REWEIGHT_CANDES: w_j = 1 / (|x_j| + eps) (:33-39); CSMP_REWEIGHT_ARD: ard_weights!(w, A, x, eps, ard_iter)
+ * on the w of the previous outer iteration, from ones (ard_function, :67) --;  xs = solve(lambda w), WARM-STARTED from x (the
+ * reference's bp has no warm start; ista has, and a cold start would spend the inner iterations on getting back to x);
+ * norm(xs - x) < min_decrease: return xs;  else x = xs.  solve = csmp_ista with the caller's maxiter, stepsize and accel.
+ * outer_maxiter = 1 is the plain csmp_ista call with the one weight lambda, bit for bit.
+ * x: the dense result, N doubles; x_loc says where b, x and w_out live (as csmp_ista).  w_out (may be NULL): the last weights (ones
+ * when no reweighting took place).  outer_done (may be NULL): the number of solves done, 1 .. outer_maxiter.  resnorm (may be NULL):
+ * ||b - A x||_2 of the returned x.  x and w stay on the device between the solves; the host reads one step norm per outer iteration.
+ * CSMP_EINVAL: a scheme that is neither, eps not positive and finite, ard_iter < 1, outer_maxiter < 1, a negative or NaN
+ * min_decrease, a negative or non-finite lambda, weights that come out NaN or Inf (:36-38), and csmp_ista's.  CSMP_ERANGE: an
+ * iterate with more than CSMP_ARD_KMAX non-zeros under CSMP_REWEIGHT_ARD (an iterate of ista is no basic solution and may have more
+ * than M: the k x k form holds for any k, eps diag(w_S ./ |x_S|) keeps it positive definite).  CSMP_ESTATE, CSMP_ENOMEM: as above. */
+#define CSMP_REWEIGHT_CANDES 0
+#define CSMP_REWEIGHT_ARD 1
+int csmp_ista_reweighted(csmp_ctx *ctx, const void *b, int b_dtype, double lambda, int scheme, double eps, int64_t ard_iter,
+                         int64_t outer_maxiter, double min_decrease, int64_t maxiter, double stepsize, int accel,
+                         double *x, int x_loc, double *w_out, int64_t *outer_done, double *resnorm);
+
 /* ------------------------------------------------------------------ dictionary analysis
  * colnorms(A): src/util.jl:2.  norms[j] = ||a_j||_2 of every column of the resident dictionary, N doubles, to host memory
  * (out_loc = CSMP_HOST) or device memory (CSMP_DEVICE; the call still returns with the work done).  Float64 on the exactly

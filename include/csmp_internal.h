@@ -32,6 +32,11 @@ int csmp_live_resources(int64_t *device_bytes, int64_t *device_blocks, int64_t *
  * (k_sweep_multi); 2: the wide pass of 2 * group_max residuals (k_sweep_wide, Float32), nontemporal loads; 3: the wide pass with
  * default-policy loads.  CSMP_TUNE_GROUP_MAX and CSMP_TUNE_TICK_GRID set their members and grid. */
 int csmp_bench_sweep(csmp_ctx *ctx, int variant, int reps, double *avg_ms);
+/* the N-pass of csmp_ard_weights alone, on the directions W = A_S L^-T the LAST csmp_ard_weights call of this context left behind (k of
+ * them): `reps` runs bracketed by one HIP event pair, the average ms of one.  variant 0: k_ard_forms, the fused kernel the library runs.
+ * variant 1: the yardstick -- the existing k_fr_rebuild_lds launched once per block of 128 directions on rho2 = |a_j|^2 (k_fr_colnorm2),
+ * then a root kernel.  max_diff (may be NULL): max_j |w_j(fused) - w_j(split)|.  CSMP_ESTATE: no such call has been made. */
+int csmp_bench_ard_forms(csmp_ctx *ctx, int variant, int reps, double eps, double *avg_ms, double *max_diff);
 /* what configure_sweep chose for the resident dictionary: loads per unit of k_sweep_gen (16 / 8 / 4); phases the residual is
  * staged in (1: one LDS image); workgroups of a stand-alone sweep and of the sweep inside the tick kernel; dynamic LDS bytes;
  * dynamic = 1: the columns are handed out at run time (k_sweep_dyn and the DYN tick), 0: split statically; columns_per_unit: 2 or 4
