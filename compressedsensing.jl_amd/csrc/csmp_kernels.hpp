@@ -2094,15 +2094,28 @@ __global__ __launch_bounds__(DYN ? kSweepDynThreads : kSweepThreads) void k_tick
 // grouped batch scheduler, host/omp.hpp).  The ring, the unit loads, the clamped ragged rows and the early first loads are
 // sweep_body_gen's; every A value is promoted once and multiplied into R accumulators, one per residual, each against its own LDS
 // image (r_slot layout).  Per residual the arithmetic is sweep_body_gen's alone: the same fma order per lane over the same KP rows,
-// the same wave_xsum, ||r||^2 in the same per-thread order, its own staged c stores and its own (max |c|, first index) partials --
-// the same bits.  A member that is already stopped (st->done & skipmask) or stops on eps in this pass is masked: it writes no c and
-// no partials.  The pass returns early only when every member is stopped.
+// wave_xsum's additions (taken in sets, see below), ||r||^2 in the same per-thread order, its own staged c stores and its own
+// (max |c|, first index) partials -- the same bits.  A member that is already stopped (st->done & skipmask) or stops on eps in this
+// pass is masked: it writes no c and no partials.  The pass returns early only when every member is stopped.
 //   waves   kMultiThreads = 512: TWO waves per SIMD share the R images (the LDS request keeps one workgroup per CU).  With one
 //           wave per SIMD (round 7's body) every pair of fmas waited for an LDS round trip, and those waits sat on the ring: a
 //           wave's next loads go out only after a unit is consumed.  With two, one wave's waits are covered by the other's issue.
 //   pairs   a wave takes the columns 2q and 2q + 1 at once (pair q = wave + 8 * workgroup, strided by the grid's waves): every
 //           image value read from the LDS feeds both columns' fmas, half the ds_read_b128 per byte of A.  Each column keeps its
 //           own accumulator chain.  A last pair of an odd N clamps its second column to N - 1 and discards it.
+//   sets    at a pair's last unit the 2R accumulators acc[column j][member i] are reduced in SETS, as sweep_body_short reduces its
+//           columns: a set of four is row_xsum(xs16(xs32(v0, v2), xs32(v1, v3))) and leaves slot q in lane row q, a set of two is
+//           xs32(v0, v1), the plain xor-16 step, row_xsum and leaves slot q in the wave's half q -- the pairs and their order are
+//           wave_xsum's for every slot (tests/xsum_twin.py), so every c has the bits of the one-column body.  The assignment:
+//             set s < R / 2 (four):  slot 2 m + j = (member 2 s + m, column j), m, j in {0, 1}
+//             the last set of an odd R (two):  slot j = (member R - 1, column j)
+//           R = 4: 4 + 4, R = 3: 4 + 2, R = 2: 4, R = 1: 2.  Per pair that is one or two butterflies instead of 2 R.  A lane keeps,
+//           per set, the arg-max of the (member, column parity) its row receives -- an increasing sequence of columns -- and the
+//           rows of a member are merged by better() at the end, which also orders two equal |c| of ONE pair; a masked member rides
+//           through its set and its results are dropped.
+//   loads   where every unit of every column is whole (KP == Mv: M = 1024, 2048, 4096, ...) the kernels run a second instantiation
+//           of the body (WHOLE) whose loads are not clamped: one address per column and unit, the U loads at constant offsets.
+//           Chosen by ONE uniform branch at the kernel's start; every other M runs the clamped instantiation.
 //   reads   the image values of the next row group are read one step ahead of the fmas (all 2R or R slots in flight together).
 //   ring    U = 4 loads per column and unit, NB = 2 units: 16 KiB per wave, 128 KiB per CU; in the steady loop each load's
 //           registers are refilled with the unit NB ahead as soon as the load is converted.
@@ -2129,7 +2142,7 @@ inline size_t sweep_multi_lds_bytes(int KP, int R) {
 }
 // bid of nblk: the workgroup's column stream; mo, nmem: its members are the entries [mo, mo + nmem) (an entry [mo + nmem, mo + R) is
 // masked like a stopped member).  NT: the ring's loads are nontemporal.
-template <typename TA, int U, int NB, int R, bool NT = true>
+template <typename TA, int U, int NB, int R, bool NT, bool WHOLE>
 __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const int bid, const int nblk, const int mo, const int nmem, double* lds) {
     using VT = typename Vec<TA>::type;
     constexpr int VEC = Vec<TA>::n;
@@ -2138,6 +2151,7 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
     constexpr int NW = kMultiThreads / kWave;
     static_assert((NB - 1) * 2 * U < 64, "the ring must fit the 6-bit vmcnt");
     static_assert(R >= 1 && R <= kGroupMax, "group size");
+    constexpr int S4 = R / 2, NS = S4 + (R & 1);  // sets of four, all sets (see `sets` above)
     unsigned live = 0;
 #pragma unroll
     for (int i = 0; i < R; ++i)
@@ -2157,20 +2171,43 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
     const int64_t NP = (N + 1) / 2;
     const int64_t q0 = (int64_t)bid * NW + wave, stride = (int64_t)nblk * NW;
     const int64_t npair = q0 < NP ? (NP - 1 - q0) / stride + 1 : 0;
-    double bestv[R];
-    int besti[R];
     const int nunit = KP / UR;  // every row of the image, as sweep_body_gen runs them (its KP is a whole number of 4-load units)
     const int Mst = KP;
     VT buf[NB][2][U];
     double acc[2][R];
 #pragma unroll
-    for (int i = 0; i < R; ++i) {
-        bestv[i] = -1.0;
-        besti[i] = 0x7fffffff;
-        acc[0][i] = acc[1][i] = 0.0;
+    for (int i = 0; i < R; ++i) acc[0][i] = acc[1][i] = 0.0;
+    // what a lane keeps per set (see `sets` above): the arg-max of the (member, column parity) its row receives, and one staged c
+    // value with its column (-1: nobody stores it).  A set of four stages 16 pairs, one per lane of a row, a set of two 32, one per
+    // lane of a half: then all 64 lanes hold a value and the wave writes them with ONE store instruction.
+    const int Ni = (int)N;  // (column indices are ints: besti, pidx)
+    double bestv[NS];
+    int besti[NS];
+    double cst[NS];
+    int ccst[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        bestv[s] = -1.0;
+        besti[s] = 0x7fffffff;
+        cst[s] = 0.0;
+        ccst[s] = -1;
     }
-    CStage<R> cs;
-    cs.init();
+    int cslot = 0;  // pairs staged since the set of two was last written, 0 .. 31
+    // the staged values of set s go out: member 2s + (lane >> 5) of a set of four, member R - 1 of the set of two
+    auto cv = [&](const int i) { return mo ? p.cvec[kGroupMax + i] : p.cvec[i]; };  // (mo is 0 or kGroupMax: no indexed kernel argument)
+    auto flush = [&](const int s) {
+        double* dst;
+        bool on;
+        if (s < S4) {
+            dst = (lane & 32) ? cv(2 * s + 1) : cv(2 * s);
+            on = (live >> (2 * s + (lane >> 5))) & 1u;
+        } else {
+            dst = cv(R - 1);
+            on = (live >> (R - 1)) & 1u;
+        }
+        if (on && ccst[s] >= 0) dst[ccst[s]] = cst[s];
+        ccst[s] = -1;
+    };
     int64_t iq = q0, cq = q0;
     int ib = 0, cb = 0;
     const int64_t T = npair * nunit;
@@ -2179,17 +2216,31 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
         if constexpr (NT) return __builtin_nontemporal_load(q);
         else return *q;
     };
+    // WHOLE: every unit of every column is whole (KP == Mv), no row is ever clamped: a unit's loads take ONE address per column
+    // (the uniform column base + the lane's 32-bit byte offset) and sit at constant offsets of 1 KiB from it
+    auto whole_base = [](const VT* pc, const int vb) {
+        return reinterpret_cast<const VT*>(reinterpret_cast<const char*>(pc) + (unsigned)vb * (unsigned)sizeof(VT));
+    };
     auto issue = [&](VT(&b)[2][U]) {
         const int64_t c0 = 2 * iq, c1 = c0 + 1 < N ? c0 + 1 : N - 1;
         // (load_unit's loads for both columns, interleaved: the pair's first requests go out together)
         const VT* p0 = reinterpret_cast<const VT*>(A + c0 * ld);
         const VT* p1 = reinterpret_cast<const VT*>(A + c1 * ld);
         const int vb = ib * (U * kWave) + lane;
+        if constexpr (WHOLE) {
+            p0 = whole_base(p0, vb);
+            p1 = whole_base(p1, vb);
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int v = vb + u * kWave;
-            b[0][u] = load(p0 + (v < nvec ? v : nvec - 1));
-            b[1][u] = load(p1 + (v < nvec ? v : nvec - 1));
+            if constexpr (WHOLE) {
+                b[0][u] = load(p0 + u * kWave);
+                b[1][u] = load(p1 + u * kWave);
+            } else {
+                const int v = vb + u * kWave;
+                b[0][u] = load(p0 + (v < nvec ? v : nvec - 1));
+                b[1][u] = load(p1 + (v < nvec ? v : nvec - 1));
+            }
         }
         if (++ib == nunit) {
             ib = 0;
@@ -2255,6 +2306,10 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
             p0 = reinterpret_cast<const VT*>(A + c0 * ld);
             p1 = reinterpret_cast<const VT*>(A + c1 * ld);
             vb = ib * (U * kWave) + lane;
+            if constexpr (WHOLE) {
+                p0 = whole_base(p0, vb);
+                p1 = whole_base(p1, vb);
+            }
             if (++ib == nunit) {
                 ib = 0;
                 iq += stride;
@@ -2279,7 +2334,10 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
                     a[j][3] = (double)b[j][u].w;
                 }
             }
-            if constexpr (REFILL) {
+            if constexpr (REFILL && WHOLE) {
+                b[0][u] = load(p0 + u * kWave);
+                b[1][u] = load(p1 + u * kWave);
+            } else if constexpr (REFILL) {
                 const int v = vb + u * kWave;
                 b[0][u] = load(p0 + (v < nvec ? v : nvec - 1));
                 b[1][u] = load(p1 + (v < nvec ? v : nvec - 1));
@@ -2297,27 +2355,45 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
                 }
             }
         }
-        if (++cb == nunit) {  // the pair's last unit: column 2q, then 2q + 1 where it exists
-            const int64_t c0 = 2 * cq;
-            const bool two = c0 + 1 < N;
+        if (++cb == nunit) {  // the pair's last unit: columns 2q and 2q + 1 (where it exists) of every member, set by set
+            const int c0 = (int)(2 * cq);
 #pragma unroll
-            for (int i = 0; i < R; ++i) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const double c = wave_xsum(acc[j][i]);
-                    acc[j][i] = 0.0;
-                    if (j == 1 && !two) continue;
-                    cs.put(lane, i, c, j);
-                    const double av = fabs(c);
-                    if (av > bestv[i]) {  // columns arrive in increasing order: '>' keeps the first maximum
-                        bestv[i] = av;
-                        besti[i] = (int)(c0 + j);
-                    }
+            for (int s = 0; s < NS; ++s) {
+                double v;
+                int col;
+                bool mine;
+                if (s < S4) {  // slots (member 2s, column 0), (2s, 1), (2s + 1, 0), (2s + 1, 1): slot q ends in lane row q
+                    v = row_xsum(xs16(xs32(acc[0][2 * s], acc[0][2 * s + 1]), xs32(acc[1][2 * s], acc[1][2 * s + 1])));
+                    col = c0 + ((lane >> 4) & 1);
+                    mine = ((lane ^ cslot) & 15) == 0;
+                } else {  // slots (member R - 1, column 0), (R - 1, 1): slot q ends in the wave's half q
+                    v = xs32(acc[0][R - 1], acc[1][R - 1]);
+                    v = row_xsum(xs16(v, v));
+                    col = c0 + (lane >> 5);
+                    mine = ((lane ^ cslot) & 31) == 0;
+                }
+                const bool have = col < Ni;  // (the second column of the last pair of an odd N)
+                if (mine) {
+                    cst[s] = v;
+                    ccst[s] = have ? col : -1;
+                }
+                const double av = fabs(v);
+                if (have && av > bestv[s]) {  // a lane's columns arrive in increasing order: '>' keeps the first maximum
+                    bestv[s] = av;
+                    besti[s] = col;
                 }
             }
-            cs.col(lane, c0);
-            cs.col(lane, two ? c0 + 1 : -1, 1);
-            cs.next(2, p.cvec + mo, live);
+#pragma unroll
+            for (int i = 0; i < R; ++i) acc[0][i] = acc[1][i] = 0.0;
+            ++cslot;
+            if ((cslot & 15) == 0) {
+#pragma unroll
+                for (int s = 0; s < S4; ++s) flush(s);
+                if (cslot == 32) {
+                    if constexpr (NS > S4) flush(S4);
+                    cslot = 0;
+                }
+            }
             cb = 0;
             cq += stride;
         }
@@ -2338,9 +2414,21 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
             if (ileft > 0) issue(buf[d]);
         }
     }
-    cs.flush(p.cvec + mo, live);
 #pragma unroll
-    for (int i = 0; i < R; ++i) argmax_put_rows(redv + i * 4 * NW, redi + i * 4 * NW, wave, lane, bestv[i], besti[i]);
+    for (int s = 0; s < NS; ++s) flush(s);
+    // member i's 4 NW partials, the layout argmax_reduce reads: a member of a set of four has ONE row per column parity and wave,
+    // so each of its two rows fills two of the wave's four entries (a repeated entry never wins better() against its twin);
+    // better() then orders the two parities as it orders the waves: larger value, then the LOWER index
+#pragma unroll
+    for (int s = 0; s < S4; ++s) {
+        if ((lane & 15) == 0) {
+            const int e = (2 * s + (lane >> 5)) * 4 * NW + wave * 4 + ((lane >> 4) & 1);
+            redv[e] = redv[e + 2] = bestv[s];
+            redi[e] = redi[e + 2] = besti[s];
+        }
+    }
+    if constexpr (NS > S4)  // the set of two: rows 0, 1 hold the even column's pair, rows 2, 3 the odd column's
+        argmax_put_rows(redv + (R - 1) * 4 * NW, redi + (R - 1) * 4 * NW, wave, lane, bestv[S4], besti[S4]);
     __syncthreads();
     if (tid < R && (live & (1u << tid)))  // thread i reduces member i's partials
         argmax_reduce(redv + tid * 4 * NW, redi + tid * 4 * NW, 4 * NW, p.pval[mo + tid], p.pidx[mo + tid], bid);
@@ -2349,7 +2437,8 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
 template <typename TA, int U, int R>
 __global__ __launch_bounds__(kMultiThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_multi(const MultiSweep<TA> p) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    sweep_body_multi<TA, U, 2, R>(p, (int)blockIdx.x, p.nblk, 0, R, lds);
+    if (p.KP == p.Mv) sweep_body_multi<TA, U, 2, R, true, true>(p, (int)blockIdx.x, p.nblk, 0, R, lds);
+    else sweep_body_multi<TA, U, 2, R, true, false>(p, (int)blockIdx.x, p.nblk, 0, R, lds);
 }
 // The WIDE pass: up to kWideMax members as two halves of n and n1 members.  The grid is a multiple of 16: workgroup b belongs to half
 // h = (b >> 3) & 1 and is stream s = (b >> 4) * 8 + (b & 7) of nblk / 2, so b and b ^ 8 walk exactly the same column pairs in the same
@@ -2362,7 +2451,8 @@ template <typename TA, int U, int R, bool NT>
 __global__ __launch_bounds__(kMultiThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_wide(const MultiSweep<TA> p) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int b = (int)blockIdx.x, h = (b >> 3) & 1;
-    sweep_body_multi<TA, U, 2, R, NT>(p, (b >> 4) * 8 + (b & 7), p.nblk >> 1, h * kGroupMax, h ? p.n1 : p.n, lds);
+    if (p.KP == p.Mv) sweep_body_multi<TA, U, 2, R, NT, true>(p, (b >> 4) * 8 + (b & 7), p.nblk >> 1, h * kGroupMax, h ? p.n1 : p.n, lds);
+    else sweep_body_multi<TA, U, 2, R, NT, false>(p, (b >> 4) * 8 + (b & 7), p.nblk >> 1, h * kGroupMax, h ? p.n1 : p.n, lds);
 }
 
 // The shared sweep of round 7 (four waves, one column each, ring U / 32 / U as the single body's), kept for Float64 dictionaries:
