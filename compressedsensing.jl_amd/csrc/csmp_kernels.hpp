@@ -2717,11 +2717,11 @@ __global__ __launch_bounds__(256) void k_finish(const double* __restrict__ R, co
 // v_readlane -- and reciprocal diagonals formed up front, so the division leaves the chain too.
 // ~0.05 us per column instead of ~0.5: this kernel closes every solve and every OMPR iteration.
 template <int NU>
-__global__ __launch_bounds__(64) void k_finish_w(const double* __restrict__ R, const double* __restrict__ z,
-                                                 const int* __restrict__ sel, const DevState* st, int kcap,
-                                                 double* __restrict__ coef, int64_t* __restrict__ out_idx,
-                                                 double* __restrict__ out_val, int64_t* __restrict__ out_nnz,
-                                                 int64_t* __restrict__ out_order, int outcap, int* __restrict__ flag_out) {
+__device__ __forceinline__ void finish_w_body(const double* __restrict__ R, const double* __restrict__ z,
+                                              const int* __restrict__ sel, const DevState* st, int kcap,
+                                              double* __restrict__ coef, int64_t* __restrict__ out_idx,
+                                              double* __restrict__ out_val, int64_t* __restrict__ out_nnz,
+                                              int64_t* __restrict__ out_order, int outcap, int* __restrict__ flag_out) {
     extern __shared__ __attribute__((aligned(16))) int ssel[];  // kcap
     const int lane = threadIdx.x, j = st->nsel;
     double yr[NU], rdr[NU], rc[NU], rn[NU];
@@ -2777,6 +2777,35 @@ __global__ __launch_bounds__(64) void k_finish_w(const double* __restrict__ R, c
         *out_nnz = j;
         if (flag_out) *flag_out = st->done | (st->uncertain ? STOP_UNCERTAIN : 0);
     }
+}
+template <int NU>
+__global__ __launch_bounds__(64) void k_finish_w(const double* __restrict__ R, const double* __restrict__ z,
+                                                 const int* __restrict__ sel, const DevState* st, int kcap,
+                                                 double* __restrict__ coef, int64_t* __restrict__ out_idx,
+                                                 double* __restrict__ out_val, int64_t* __restrict__ out_nnz,
+                                                 int64_t* __restrict__ out_order, int outcap, int* __restrict__ flag_out) {
+    finish_w_body<NU>(R, z, sel, st, kcap, coef, out_idx, out_val, out_nnz, out_order, outcap, flag_out);
+}
+
+// The end of a batch round: the solves of ALL members of a context in ONE launch, workgroup m the single wave of k_finish_w<4> for
+// member m (kcap <= 256, no insertion order) -- its own R, z, selection and outputs, so every member's bits are k_finish_w's.  One
+// by one in stream order the waves of a round ran behind each other, ~150 us each at 256 columns, with nothing else on the stream.
+struct FinishMember {
+    const double* R; const double* z; const int* sel; const DevState* st;
+    double* coef; int64_t* out_idx; double* out_val; int64_t* out_nnz; int* flag_out;
+    int kcap;  // the member's own: the leading dimension of its R
+};
+constexpr int kFinishGroupMax = 3 * kWideMax;  // the slots of a context
+struct GroupFinish {
+    FinishMember m[kFinishGroupMax];
+    int n, outcap;
+};
+static_assert(sizeof(GroupFinish) <= 4096, "kernel arguments");
+__global__ __launch_bounds__(64) void k_finish_group(const GroupFinish a) {
+    const int b = (int)blockIdx.x;  // (dynamic LDS: the largest kcap of the members)
+    if (b >= a.n) return;
+    const FinishMember& f = a.m[b];
+    finish_w_body<4>(f.R, f.z, f.sel, f.st, f.kcap, f.coef, f.out_idx, f.out_val, f.out_nnz, nullptr, a.outcap, f.flag_out);
 }
 
 

@@ -75,6 +75,8 @@ struct BatchIO {
     }
     // c's solution into signal s's outputs (sflag: its stop flags, or null)
     int emit(csmp_ctx* c, int64_t s, int* sflag) const { return launch_finish(c, d_idx + s * k, d_val + s * k, d_nnz + s, nullptr, (int)k, sflag); }
+    // emit's arguments for solver sv as a member of a round's finish launch (launch_finish_group)
+    FinishMember member(const Solver& sv, int64_t s, int* sflag) const { return finish_member(sv, d_idx + s * k, d_val + s * k, d_nnz + s, sflag); }
     // the end of the call: a host caller's outputs come back (after a success only), and this context's stream is drained
     int done(int rc) {
         if (out_loc == CSMP_HOST) {

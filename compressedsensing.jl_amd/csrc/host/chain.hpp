@@ -333,6 +333,25 @@ static int launch_finish(csmp_ctx* ctx, int64_t* d_idx, double* d_val, int64_t* 
     return CSMP_OK;
 }
 
+// the arguments of launch_finish for solver s as a member of a round's finish launch
+static FinishMember finish_member(const Solver& s, int64_t* d_idx, double* d_val, int64_t* d_nnz, int* d_flag) {
+    return FinishMember{s.R, s.z, s.sel, s.st, s.coef, d_idx, d_val, d_nnz, d_flag, s.kcap};
+}
+// whether launch_finish runs solver s as the single wave of k_finish_w<4>: the form k_finish_group holds
+static bool finish_groupable(const Solver& s) { return s.kcap >= 1 && s.kcap <= 256; }
+// launch_finish for the a.n members of a round on ctx's stream at once (k_finish_group); every member finish_groupable
+static int launch_finish_group(csmp_ctx* ctx, const GroupFinish& a) {
+    if (a.n < 1 || a.n > kFinishGroupMax) return fail(ctx, CSMP_ESTATE, "launch_finish_group: members out of range");
+    int kcap = 0;
+    for (int m = 0; m < a.n; ++m) {
+        if (a.m[m].kcap < 1 || a.m[m].kcap > 256) return fail(ctx, CSMP_ESTATE, "launch_finish_group: a member beyond the single-wave form");
+        kcap = std::max(kcap, a.m[m].kcap);
+    }
+    hipLaunchKernelGGL(k_finish_group, dim3(a.n), dim3(64), (size_t)kcap * sizeof(int), ctx->stream, a);
+    HIPCHECK(hipGetLastError());
+    return CSMP_OK;
+}
+
 static int download_result(csmp_ctx* ctx, int outcap, int64_t* idx, double* val, int64_t* nnz, int64_t* order) {
     Solver& s = ctx->s;
     std::vector<int64_t> hi((size_t)outcap), ho((size_t)outcap);

@@ -369,6 +369,36 @@ static int batch_impl(csmp_ctx* ctx, BatchIO& io, bool isfr, double eps, double 
                     }
             return CSMP_OK;
         };
+        // The end of a round: ONE finish launch per context for all its members (k_finish_group) -- member by member in stream order
+        // the single waves ran behind each other, twelve of ~150 us on pipeline A at 18 signals and k = 256, after the last pass.
+        // Supports beyond the single-wave form (kcap > 256: launch_finish's block back substitution) keep one launch_finish each.
+        auto finish_round = [&](const PlanRound& r) -> int {
+            csmp_ctx* cs[2] = {ctx, tw};
+            for (int p = 0; p < 2; ++p) {
+                if (!cs[p]) continue;
+                activate_slot(cs[p], 0);  // (slot_ptr)
+                GroupFinish a;
+                a.n = 0;
+                a.outcap = (int)k;
+                bool group = true;
+                for (int g = 0; g < 3; ++g)
+                    for (int m = 0; m < r.g[p][g].size; ++m) {
+                        const Solver& sv = *slot_ptr(cs[p], g + 3 * m);
+                        group = group && finish_groupable(sv) && a.n < kFinishGroupMax;
+                        if (!group) continue;
+                        const int64_t sgn = r.g[p][g].first + m;
+                        a.m[a.n++] = io.member(sv, sgn, sigflags + sgn);
+                    }
+                if (!group) {  // one launch_finish per member, as ever
+                    PlanRound own = r;
+                    for (int g = 0; g < 3; ++g) own.g[1 - p][g].size = 0;
+                    CHECK(each_member(own, finish));
+                } else if (a.n > 0) {
+                    CHECK(twin_rc(ctx, cs[p], launch_finish_group(cs[p], a)));
+                }
+            }
+            return CSMP_OK;
+        };
         // Wide groups keep the plan's dealing over both pipelines (18 signals: groups 0 and 2 on A, 1 on B).  Measured on the benchmark,
         // atoms/s at 18 / 20 signals, two runs each: 2 + 1 on 256 workgroups 26 087, 26 176 / 27 622, 27 735; three groups on ONE pipeline
         // (csmp_tune group_wide 2) 25 257, 25 071 / 26 958, 27 060 -- its append launches have no other pipeline's sweep to run under.
@@ -376,7 +406,7 @@ static int batch_impl(csmp_ctx* ctx, BatchIO& io, bool isfr, double eps, double 
         for (const PlanRound& r : batch_plan(nsig, sched, members, wide && ctx->tune_group_wide == 2)) {
             CHECK(each_member(r, init));
             CHECK(ctx->dtype == CSMP_F32 ? run_round<float>(r, ctx, tw, isfr, k, eps, p2) : run_round<double>(r, ctx, tw, isfr, k, eps, p2));
-            CHECK(each_member(r, finish));
+            CHECK(finish_round(r));
         }
         return CSMP_OK;
     };
