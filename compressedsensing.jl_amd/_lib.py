@@ -85,6 +85,10 @@ SIGNATURES = {
     "csmp_ard_weights": (C.c_int, [vp, vp, vp, C.c_double, i64, vp, C.c_int]),
     "csmp_ista_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, i64, i64, C.c_double, i64, C.c_double, C.c_int, vp, C.c_int, vp,
                                        C.POINTER(i64), C.POINTER(C.c_double)]),
+    "csmp_bp": (C.c_int, [vp, vp, C.c_int, vp, i64, C.c_double, i64, C.c_double, i64, vp, C.c_int, C.POINTER(i64), C.POINTER(C.c_double),
+                          C.POINTER(C.c_int)]),
+    "csmp_bp_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_double, i64, i64, C.c_double, C.c_double, i64, C.c_double, i64, vp, C.c_int, vp,
+                                     C.POINTER(i64), C.POINTER(C.c_double)]),
     "csmp_colnorms": (C.c_int, [vp, vp, C.c_int]),
     "csmp_cumbabel": (C.c_int, [vp, i64, C.c_int, vp, vp]),
     "csmp_sweep": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -98,6 +102,7 @@ INTERNAL_SIGNATURES = {
     "csmp_profile_read": (C.c_int, [vp, C.POINTER(i64), C.POINTER(C.c_double), C.c_int]),
     "csmp_bench_sweep": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "csmp_bench_ard_forms": (C.c_int, [vp, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "csmp_bp_rowgram": (C.c_int, [vp, vp, C.c_int]),
     "csmp_profile_overhead": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
     "csmp_live_resources": (C.c_int, [C.POINTER(i64)] * 6),
     "csmp_profile_window": (C.c_int, [vp, C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
@@ -108,12 +113,13 @@ INTERNAL_SIGNATURES = {
     "csmp_batch_layout": (C.c_int, [vp, C.POINTER(i64), C.POINTER(C.c_int)]),
     "csmp_batch_screen_kernel": (C.c_char_p, [vp]),
 }
-TUNE = {"sweep_grid": 2, "sweep_unit": 3, "tick_grid": 4, "batch_budget_mib": 5, "diag_split": 6, "swap_refuse": 7, "rebuild_direct": 8, "sweep_dyn": 9, "tick_order": 10, "claim_pools": 11, "pipelines": 12, "pair_lds_kib": 13, "pair_split": 14, "sweep_lds_kib": 15, "sweep_short": 16, "phase_rows": 17, "fail_alloc": 18, "screen_static": 19, "group_max": 20, "group_wide": 21}  # CSMP_TUNE_* (include/csmp_internal.h)
+TUNE = {"sweep_grid": 2, "sweep_unit": 3, "tick_grid": 4, "batch_budget_mib": 5, "diag_split": 6, "swap_refuse": 7, "rebuild_direct": 8, "sweep_dyn": 9, "tick_order": 10, "claim_pools": 11, "pipelines": 12, "pair_lds_kib": 13, "pair_split": 14, "sweep_lds_kib": 15, "sweep_short": 16, "phase_rows": 17, "fail_alloc": 18, "screen_static": 19, "group_max": 20, "group_wide": 21, "rowgram_scalar": 22}  # CSMP_TUNE_* (include/csmp_internal.h)
 
 COMM_ID_BYTES = 128  # CSMP_COMM_ID_BYTES
 BABEL_KMAX = 1024  # CSMP_BABEL_KMAX
 ARD_KMAX = 1024  # CSMP_ARD_KMAX
 REWEIGHT_CANDES, REWEIGHT_ARD = 0, 1  # CSMP_REWEIGHT_*
+BP_CONVERGED, BP_FACTORED = 1, 2  # CSMP_BP_*
 
 
 def live_resources():
@@ -727,6 +733,78 @@ class Context:
                   C.c_double(eps), i64(int(ard_iter)), i64(int(outer_maxiter)), C.c_double(min_decrease), i64(int(maxiter)), C.c_double(stepsize),
                   int(bool(accel)), vp(x.data_ptr()), DEVICE, vp(w.data_ptr() if w is not None else 0), C.byref(done), C.byref(rn))
         return rn.value, int(done.value)
+
+    # ---- basis pursuit
+    def _bp_info(self, it, rn, flags):
+        return {"iterations": int(it.value), "converged": bool(flags.value & BP_CONVERGED), "factored": bool(flags.value & BP_FACTORED),
+                "resnorm": rn.value}
+
+    def bp(self, b, w=1.0, rho=1.0, maxiter=16384, tol=1e-8, check_every=32):
+        """csmp_bp on a host signal: (dense z, Float64[N]; info = iterations, converged, factored, resnorm).  w: one weight or N of them.
+        The first call on a dictionary forms and factorises A Aᵀ: M² + (2M)² doubles of device memory (128 MiB + 512 MiB at M = 4096), kept
+        until the dictionary changes."""
+        b = self._b(b)
+        w, _, _ = self._ista_args(w, None, None)
+        x = np.zeros(max(self.N, 1), np.float64)
+        rn, it, flags = C.c_double(0), i64(0), C.c_int(0)
+        self.call("csmp_bp", ptr(b), dtype_code(b.dtype), ptr(w), i64(len(w)), C.c_double(rho), i64(int(maxiter)), C.c_double(tol),
+                  i64(int(check_every)), ptr(x), HOST, C.byref(it), C.byref(rn), C.byref(flags))
+        return x[:self.N], self._bp_info(it, rn, flags)
+
+    def bp_device(self, b, w, x, rho=1.0, maxiter=16384, tol=1e-8, check_every=32):
+        """torch CUDA tensors: b (M,) float32 / float64, x (N,) float64 receives the dense result.  Returns info; the work is done when the
+        call returns."""
+        import torch
+        if not (b.is_cuda and b.is_contiguous() and b.shape == (self.M,) and b.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "b must be a contiguous CUDA vector of length size(A, 1), float32 or float64")
+        if not (x.is_cuda and x.is_contiguous() and x.shape == (self.N,) and x.dtype == torch.float64):
+            raise CsmpError(EDIM, "x must be a contiguous CUDA float64 vector of length size(A, 2)")
+        w, _, _ = self._ista_args(w, None, None)
+        rn, it, flags = C.c_double(0), i64(0), C.c_int(0)
+        self.call("csmp_bp", vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64, ptr(w), i64(len(w)), C.c_double(rho), i64(int(maxiter)),
+                  C.c_double(tol), i64(int(check_every)), vp(x.data_ptr()), DEVICE, C.byref(it), C.byref(rn), C.byref(flags))
+        return self._bp_info(it, rn, flags)
+
+    def bp_reweighted(self, b, scheme, eps=1e-2, ard_iter=8, outer_maxiter=8, min_decrease=1e-8, rho=1.0, maxiter=16384, tol=1e-8, check_every=32,
+                      return_weights=False):
+        """csmp_bp_reweighted on a host signal: (dense z, ||b - A z||, solves done[, the last weights]).  scheme: "candes" / "ard"."""
+        b = self._b(b)
+        x = np.zeros(max(self.N, 1), np.float64)
+        w = np.zeros(max(self.N, 1), np.float64) if return_weights else None
+        rn, done = C.c_double(0), i64(0)
+        self.call("csmp_bp_reweighted", ptr(b), dtype_code(b.dtype), _scheme(scheme), C.c_double(eps), i64(int(ard_iter)), i64(int(outer_maxiter)),
+                  C.c_double(min_decrease), C.c_double(rho), i64(int(maxiter)), C.c_double(tol), i64(int(check_every)), ptr(x), HOST, ptr(w),
+                  C.byref(done), C.byref(rn))
+        res = (x[:self.N], rn.value, int(done.value))
+        return res + (w[:self.N],) if return_weights else res
+
+    def bp_reweighted_device(self, b, scheme, x, w=None, eps=1e-2, ard_iter=8, outer_maxiter=8, min_decrease=1e-8, rho=1.0, maxiter=16384,
+                             tol=1e-8, check_every=32):
+        """torch CUDA tensors: b (M,) float32 / float64; x and (optionally) w (N,) float64 receive the result and the last weights.
+        Returns (||b - A z||, solves done)."""
+        import torch
+        if not (b.is_cuda and b.is_contiguous() and b.shape == (self.M,) and b.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "b must be a contiguous CUDA vector of length size(A, 1), float32 or float64")
+        for v in (x,) if w is None else (x, w):
+            if not (v.is_cuda and v.is_contiguous() and v.shape == (self.N,) and v.dtype == torch.float64):
+                raise CsmpError(EDIM, "x and w must be contiguous CUDA float64 vectors of length size(A, 2)")
+        rn, done = C.c_double(0), i64(0)
+        self.call("csmp_bp_reweighted", vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64, _scheme(scheme), C.c_double(eps),
+                  i64(int(ard_iter)), i64(int(outer_maxiter)), C.c_double(min_decrease), C.c_double(rho), i64(int(maxiter)), C.c_double(tol),
+                  i64(int(check_every)), vp(x.data_ptr()), DEVICE, vp(w.data_ptr() if w is not None else 0), C.byref(done), C.byref(rn))
+        return rn.value, int(done.value)
+
+    def bp_rowgram(self, device=False):
+        """csmp_bp_rowgram (csmp_internal.h): G = A Aᵀ as k_rowgram forms it, Float64 (M, M) -- a numpy array, or (device=True) a torch
+        CUDA tensor"""
+        if device:
+            import torch
+            out = torch.empty((self.M, self.M), dtype=torch.float64, device="cuda")
+            self.call("csmp_bp_rowgram", vp(out.data_ptr()), DEVICE)
+            return out
+        out = np.zeros((self.M, self.M), np.float64)
+        self.call("csmp_bp_rowgram", ptr(out), HOST)
+        return out
 
     # ---- dictionary analysis
     def colnorms(self, device=False):

@@ -16,6 +16,7 @@ Same names, argument meaning and error behaviour as the reference (paths relativ
     MP / OMP / GOMP functors with update!    src/matchingpursuit.jl:10-31,44-70,95-123
     argmaxinner!(P[, k])                     src/matchingpursuit.jl:181-193
     ista(A, b, λ | w[, x]; maxiter, stepsize) / fista(...) / shrinkage(x, α)   src/basispursuit.jl:144,164-204
+    bp(A, b[, w]) = basispursuit / bp_candes(A, b, ε) / bp_ard(A, b, ε)         src/basispursuit.jl:1-74
     colnorms(A) / coherence(A) / babel(A, k) / cumbabel(A, k)               src/util.jl:2,96-115
 
 `A` is either a numpy matrix (uploaded to HBM for the duration of the call) or a `Dictionary`
@@ -260,6 +261,93 @@ def ista_ard(A, b, lam, eps=1e-2, *, maxiter=8, min_decrease=1e-8, inner_maxiter
     if not _is_int(iter) or iter < 1:
         raise ValueError(f"iter = {iter} has to be at least 1")
     return _ista_reweighted(A, b, lam, "ard", eps, maxiter, min_decrease, inner_maxiter, stepsize, accel, return_weights, int(iter))
+
+
+# ------------------------------------------------------------------------------------ basis pursuit
+def _bp_knobs(A, rho, maxiter, tol, check_every):
+    M, N, _ = _meta(A)
+    if M > N:
+        raise ValueError(f"size(A) = {(M, N)}: A Aᵀ is singular when size(A, 1) > size(A, 2)")
+    if not (rho > 0 and np.isfinite(rho)):
+        raise ValueError(f"rho = {rho} has to be positive and finite")
+    if not (tol > 0 and np.isfinite(tol)):
+        raise ValueError(f"tol = {tol} has to be positive and finite")
+    if not maxiter >= 0:
+        raise ValueError(f"maxiter = {maxiter} has to be non-negative")
+    if not _is_int(check_every) or check_every < 1:
+        raise ValueError(f"check_every = {check_every} has to be at least 1")
+    return M, N
+
+
+def bp(A, b, w=None, *, rho=1.0, maxiter=16384, tol=1e-8, check_every=32, return_info=False):
+    """bp(A, b[, w]) = basispursuit (src/basispursuit.jl:1-16): min Σ w_j |x_j| subject to A x = b, w = ones by default.  ADMM on the
+    split x = z with one Cholesky factorisation of A Aᵀ per Dictionary (kept until its dictionary changes: M² + (2M)² doubles of
+    device memory, 128 MiB + 512 MiB at M = 4096); every check_every iterations the primal and dual residuals are read, and the iteration
+    stops once both are below tol.  Returns the exactly sparse z; return_info=True: (z, info) with info = {iterations, converged,
+    factored, resnorm = ‖b − A z‖}.  Reaching maxiter is no error (converged is False).  A without full row rank is a ValueError."""
+    M, N = _bp_knobs(A, rho, maxiter, tol, check_every)
+    w = np.ones(1) if w is None else np.atleast_1d(np.asarray(w, dtype=np.float64))
+    if w.ndim != 1 or len(w) not in (1, N):
+        raise ValueError(f"length(w) = {w.shape} but size(A, 2) = {N}")
+    if not np.all((w >= 0) & np.isfinite(w)):
+        raise ValueError("the weights have to be non-negative and finite")
+    D, tmp = _dict(A)
+    try:
+        try:
+            xd, info = D.ctx.bp(b, w, float(rho), int(maxiter), float(tol), int(check_every))
+        except CsmpError as e:
+            if e.code == _lib.EINVAL and "positive definite" in str(e):
+                raise ValueError(str(e)) from None
+            raise
+        nz = np.flatnonzero(xd)
+        x = SparseVector(N, nz, xd[nz])
+        return (x, info) if return_info else x
+    finally:
+        if tmp:
+            D.close()
+
+
+basispursuit = bp
+
+
+def _bp_reweighted(A, b, scheme, eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights, ard_iter=8):
+    M, N = _bp_knobs(A, rho, inner_maxiter, tol, check_every)
+    if not (eps > 0 and np.isfinite(eps)):
+        raise ValueError(f"eps = {eps} has to be positive and finite")
+    if not _is_int(maxiter) or maxiter < 1:
+        raise ValueError(f"maxiter = {maxiter} has to be at least 1")
+    if not min_decrease >= 0:
+        raise ValueError(f"min_decrease = {min_decrease} has to be non-negative")
+    D, tmp = _dict(A)
+    try:
+        try:
+            out = D.ctx.bp_reweighted(b, scheme, float(eps), ard_iter, int(maxiter), float(min_decrease), float(rho), int(inner_maxiter), float(tol),
+                                      int(check_every), return_weights)
+        except CsmpError as e:
+            if e.code == _lib.EINVAL and "positive definite" in str(e):
+                raise ValueError(str(e)) from None
+            raise
+        nz = np.flatnonzero(out[0])
+        x = SparseVector(N, nz, out[0][nz])
+        return (x, out[3]) if return_weights else x
+    finally:
+        if tmp:
+            D.close()
+
+
+def bp_candes(A, b, eps=1e-2, *, maxiter=8, min_decrease=1e-8, rho=1.0, inner_maxiter=16384, tol=1e-8, check_every=32, return_weights=False):
+    """bp_candes(A, b, ε; maxiter, min_decrease) (src/basispursuit.jl:18-45): x = bp(A, b); up to maxiter − 1 times w_j = 1 / (|x_j| + ε),
+    xs = bp(A, b, w) warm-started from the previous solve's iterates, stop once ‖xs − x‖ < min_decrease.  rho, inner_maxiter, tol,
+    check_every: bp's, for every solve.  return_weights=True: (x, the last w)."""
+    return _bp_reweighted(A, b, "candes", eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights)
+
+
+def bp_ard(A, b, eps=1e-2, *, maxiter=8, min_decrease=1e-8, iter=8, rho=1.0, inner_maxiter=16384, tol=1e-8, check_every=32, return_weights=False):
+    """bp_ard(A, b, ε; maxiter, min_decrease, iter) (src/basispursuit.jl:18-31,49-74): as bp_candes with ard_weights!(w, A, x, ε, iter)
+    on the weights of the previous outer iteration (from ones); an iterate with more than min(size(A, 1), 1024) non-zeros is refused."""
+    if not _is_int(iter) or iter < 1:
+        raise ValueError(f"iter = {iter} has to be at least 1")
+    return _bp_reweighted(A, b, "ard", eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights, int(iter))
 
 
 # ------------------------------------------------------------------------------------ dictionary analysis

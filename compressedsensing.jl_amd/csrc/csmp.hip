@@ -19,6 +19,7 @@
 #include "csmp_ista.hpp"
 #include "csmp_analysis.hpp"
 #include "csmp_reweight.hpp"
+#include "csmp_bp.hpp"
 
 #include <algorithm>
 #include <iterator>
@@ -56,5 +57,6 @@ using namespace csmp;
 #include "host/ista.hpp"
 #include "host/analysis.hpp"
 #include "host/reweight.hpp"
+#include "host/bp.hpp"
 #include "host/measure.hpp"
 #include "host/rccl.hpp"

@@ -166,6 +166,18 @@ struct RwBuf {
     int np = 0, nsplit = 0;  // columns the support's buffers were made for (0: none), and k_gram's row slices
 };
 
+// basis pursuit (csmp_bp.hpp, host/bp.hpp): G = A A' (M x M), the augmented matrix [G | I] the blocked Cholesky turns into R beside R^-T
+// (np = M rounded up to whole 64-column tiles, leading dimension 2 np; R^-1 sits in its rows from np on), the verdict of the
+// factorisation and the M-vectors of the iteration, made on first use, sized by the dictionary: all of them, or none
+struct BpBuf {
+    double *G = nullptr, *Gm = nullptr, *pivref = nullptr, *Dfac = nullptr, *vec = nullptr, *rpart = nullptr, *res = nullptr;
+    DevState* st = nullptr;
+    int M = 0, np = 0;      // rows the buffers were made for (0: none)
+    int Mp = 0;             // length of each of the six M-vectors p, q, e, v, y, g in vec (zero beyond M: the sweep reads Mv rows)
+    bool factored = false;  // G and its factor belong to the current dictionary
+    bool notpd = false;     // ... and the factorisation met a pivot that is not positive to working precision
+};
+
 struct csmp_ctx;
 // Subspace Pursuit as a resumable job: see host/gomp_sp.hpp
 struct SpJob {
@@ -237,6 +249,7 @@ struct csmp_ctx {
     int claim_pools = 8;     // counters a workgroup of the dynamic sweep finds empty in a row before it stops (its own, then the following workgroups')
     int tune_rebuild_direct = 0;  // csmp_tune: the oblivious start's Q'A pass reads its directions from L2 (k_fr_rebuild) instead of the LDS
     int tune_swap_refuse = 0;  // csmp_tune: OMPR's inverse-Gram exchanges fail their guard (tests walk the fallback to the QR path)
+    int tune_rowgram_scalar = 0;  // csmp_tune: k_rowgram without 16-byte loads
     int tune_diag_split = 0;  // csmp_tune: fused kernels run as one launch per part (a kernel trace then shows the parts)
     int64_t tune_batch_budget_mib = 0;  // csmp_tune: HBM the batched path's per-signal state may take (MiB), 0 = what is free  // csmp_tune (include/csmp_internal.h): measurement overrides, 0 = automatic
     // options (csmp_set_option, include/csmp.h)
@@ -271,6 +284,7 @@ struct csmp_ctx {
     IstaBuf ista;
     AnalysisBuf analysis;
     RwBuf rw;
+    BpBuf bp;
     // profiling
     bool prof = false;
     int prof_every = 1;       // time every n-th sweep launch only (an event pair costs a few us of stream time)

@@ -247,6 +247,7 @@ static int dict_forget(csmp_ctx* ctx) {
     ista_free(ctx->ista);
     analysis_free(ctx->analysis);
     rw_free(ctx->rw);
+    bp_free(ctx->bp);
     return CSMP_OK;
 }
 

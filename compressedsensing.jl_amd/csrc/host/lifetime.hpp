@@ -102,6 +102,11 @@ static void rw_free(RwBuf& t) {
     t = RwBuf();
 }
 
+static void bp_free(BpBuf& t) {
+    dfree(t.G); dfree(t.Gm); dfree(t.pivref); dfree(t.Dfac); dfree(t.vec); dfree(t.rpart); dfree(t.res); dfree(t.st);
+    t = BpBuf();
+}
+
 static void dict_release(csmp_ctx* ctx) {
     if (ctx->share && --ctx->share->refs == 0) {
         if (ctx->share->kind == 0) (void)hipFree(ctx->share->p);
@@ -127,6 +132,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     ista_free(ctx->ista);
     analysis_free(ctx->analysis);
     rw_free(ctx->rw);
+    bp_free(ctx->bp);
     if (ctx->comm) (void)csmp_comm_free(ctx);
     for (auto& t : ctx->twins) {
         if (t) (void)csmp_destroy(t);

@@ -267,6 +267,7 @@ extern "C" int csmp_tune(csmp_ctx* ctx, int key, int64_t value) {
         case CSMP_TUNE_SCREEN_STATIC: ctx->tune_screen_static = value == 1 ? 1 : 0; return CSMP_OK;
         case CSMP_TUNE_PAIR_SPLIT: ctx->tune_pair_split = value == 1 ? 1 : 0; return CSMP_OK;
         case CSMP_TUNE_FAIL_ALLOC: ctx->tune_fail_alloc = (int)value; return CSMP_OK;
+        case CSMP_TUNE_ROWGRAM_SCALAR: ctx->tune_rowgram_scalar = value == 1 ? 1 : 0; return CSMP_OK;
         case CSMP_TUNE_GROUP_MAX:
             if (value > kGroupMax) return fail(ctx, CSMP_EINVAL, "csmp_tune: group_max must be 0 (what the LDS holds) or 1 .. 4");
             ctx->tune_group_max = (int)value;

@@ -186,7 +186,7 @@ fista(A::MatOrDict, b::AbstractVector, λ::Real, x::AbstractVector = spzeros(siz
 
 # ---------------------------------------------------------------------------------- reweighted l1
 # src/basispursuit.jl:18-74: candes_weights!, ard_weights! and basispursuit_reweighting with ista / fista as the solver of
-# ‖b - A x‖² + λ Σ w_j |x_j| (the reference's bp / bpd need an LP / SOCP solver and are not part of libcsmp).
+# ‖b - A x‖² + λ Σ w_j |x_j| (the loops around bp itself: bp_candes / bp_ard below; bpd needs an SOCP solver and is not part of libcsmp).
 const CSMP_ARD_KMAX = 1024
 const CSMP_REWEIGHT_CANDES = 0
 const CSMP_REWEIGHT_ARD = 1
@@ -226,6 +226,46 @@ ista_candes(A::MatOrDict, b::AbstractVector, λ::Real, ε::Real = 1e-2; maxiter:
 ista_ard(A::MatOrDict, b::AbstractVector, λ::Real, ε::Real = 1e-2; maxiter::Int = 8, min_decrease::Real = 1e-8, inner_maxiter::Int = 1024,
          stepsize::Real = 1e-2, accel::Bool = false, return_weights::Bool = false, iter::Int = 8) =
     ista_reweighted(A, b, λ, CSMP_REWEIGHT_ARD, ε, iter, maxiter, min_decrease, inner_maxiter, stepsize, accel, return_weights)
+
+# ---------------------------------------------------------------------------------- basis pursuit
+# src/basispursuit.jl:1-74: bp(A, b[, w]) = basispursuit -- min Σ w_j |x_j| subject to A x = b, by ADMM with one Cholesky factorisation of
+# A Aᵀ per Dictionary (csmp_bp, include/csmp.h) -- and bp_candes / bp_ard, basispursuit_reweighting around it (csmp_bp_reweighted).
+const CSMP_BP_CONVERGED = 1
+const CSMP_BP_FACTORED = 2
+function bp_call(A::MatOrDict, b::AbstractVector, w::Vector{Float64}, rho::Real, maxiter::Int, tol::Real, check_every::Int, return_info::Bool)
+    D = dict(A)
+    bb, bt = bvec(b)
+    xd = zeros(Float64, size(D, 2))
+    it, rn, flags = Ref{Int64}(0), Ref{Cdouble}(0), Ref{Cint}(0)
+    GC.@preserve bb w xd check(D, ccall((:csmp_bp, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Int64, Cdouble, Int64, Cdouble, Int64, Ptr{Cdouble}, Cint, Ref{Int64}, Ref{Cdouble}, Ref{Cint}),
+        D.ctx, bb, bt, w, length(w), rho, maxiter, tol, check_every, xd, CSMP_HOST, it, rn, flags))
+    info = (iterations = Int(it[]), converged = flags[] & CSMP_BP_CONVERGED != 0, factored = flags[] & CSMP_BP_FACTORED != 0, resnorm = rn[])
+    return return_info ? (sparse(xd), info) : sparse(xd)
+end
+bp(A::MatOrDict, b::AbstractVector; rho::Real = 1.0, maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32, return_info::Bool = false) =
+    bp_call(A, b, Float64[1.0], rho, maxiter, tol, check_every, return_info)
+bp(A::MatOrDict, b::AbstractVector, w::AbstractVector; rho::Real = 1.0, maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32,
+   return_info::Bool = false) = bp_call(A, b, convert(Vector{Float64}, w), rho, maxiter, tol, check_every, return_info)
+const basispursuit = bp
+function bp_reweighted(A::MatOrDict, b::AbstractVector, scheme::Integer, ε::Real, ard_iter::Int, maxiter::Int, min_decrease::Real, rho::Real,
+                       inner_maxiter::Int, tol::Real, check_every::Int, return_weights::Bool)
+    D = dict(A)
+    bb, bt = bvec(b)
+    xd, w = zeros(Float64, size(D, 2)), zeros(Float64, size(D, 2))
+    done, rn = Ref{Int64}(0), Ref{Cdouble}(0)
+    GC.@preserve bb xd w check(D, ccall((:csmp_bp_reweighted, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cdouble, Int64, Int64, Cdouble, Cdouble, Int64, Cdouble, Int64, Ptr{Cdouble}, Cint, Ptr{Cdouble},
+         Ref{Int64}, Ref{Cdouble}),
+        D.ctx, bb, bt, Cint(scheme), ε, ard_iter, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, xd, CSMP_HOST, w, done, rn))
+    return return_weights ? (sparse(xd), w) : sparse(xd)
+end
+bp_candes(A::MatOrDict, b::AbstractVector, ε::Real = 1e-2; maxiter::Int = 8, min_decrease::Real = 1e-8, rho::Real = 1.0, inner_maxiter::Int = 16384,
+          tol::Real = 1e-8, check_every::Int = 32, return_weights::Bool = false) =
+    bp_reweighted(A, b, CSMP_REWEIGHT_CANDES, ε, 8, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights)
+bp_ard(A::MatOrDict, b::AbstractVector, ε::Real = 1e-2; maxiter::Int = 8, min_decrease::Real = 1e-8, iter::Int = 8, rho::Real = 1.0,
+       inner_maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32, return_weights::Bool = false) =
+    bp_reweighted(A, b, CSMP_REWEIGHT_ARD, ε, iter, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights)
 
 # ---------------------------------------------------------------------------------- dictionary analysis
 # src/util.jl:2,96-115: colnorms, coherence, babel, cumbabel.  The inner products are raw, as in the reference (which assumes unit-norm

@@ -394,7 +394,8 @@ int csmp_ista(csmp_ctx *ctx, const void *b, int b_dtype, const double *w, int64_
 
 /* ------------------------------------------------------------------ reweighted l1
  * candes_weights! / ard_weights! / basispursuit_reweighting: src/basispursuit.jl:18-74 (bp_candes, bp_ard; bpd_candes, bpd_ard :102-124),
- * with ista / fista as the inner solver -- the reference's bp / bpd need an LP / SOCP solver and are not part of this library.
+ * with ista / fista as the inner solver (the reference's own inner solver, bp, is csmp_bp below; bpd needs an SOCP solver and is not
+ * part of this library).
  *
  * ard_weights!(w, A, x, eps, iter) (:49-65): `iter` times over,  d = |x| ./ w;  K = eps I + A diag(d) A';
  * w_j = sqrt(max(a_j' K^-1 a_j, 0)) for every atom.  x, w_in, w_out: N doubles each, all three in host memory (loc = CSMP_HOST) or all
@@ -427,6 +428,42 @@ int csmp_ard_weights(csmp_ctx *ctx, const double *x, const double *w_in, double 
 int csmp_ista_reweighted(csmp_ctx *ctx, const void *b, int b_dtype, double lambda, int scheme, double eps, int64_t ard_iter,
                          int64_t outer_maxiter, double min_decrease, int64_t maxiter, double stepsize, int accel,
                          double *x, int x_loc, double *w_out, int64_t *outer_done, double *resnorm);
+
+/* ------------------------------------------------------------------ basis pursuit
+ * basispursuit(A, b[, w]) = bp: src/basispursuit.jl:1-16.  min sum_j w_j |x_j| subject to A x = b, by ADMM on the split x = z -- no
+ * LP solver: with G = A A' = R'R (formed and factorised ONCE per dictionary, kept by the context until csmp_set_dictionary), the scaled
+ * dual u, the penalty rho, shrink(t, a) = sign(t) max(|t| - a, 0), and p = A z, q = A u carried as M-vectors, one iteration is
+ *     e = p - q - b;   y = G^-1 e;   c = A' y;   t = z - c;   z+ = shrink(t, w / rho);   u+ = t - z+;
+ *     r = b - A z+;   p+ = b - r;   q+ = p - G y - p+
+ * -- one pass over A, one over the non-zeros of z+, three M x M matrix-vector products.  Start: z = u = 0.  Every check_every
+ * iterations the host reads ||u+ - u|| (primal residual) and rho ||z+ - z|| (dual residual) and stops when both are < tol; reaching
+ * maxiter is not an error.  The result is z: exactly sparse; the feasible but dense x of the iteration is not returned.
+ * w, nw: nw = 1 is one weight for every atom, nw = size(A,2) one weight per atom; anything else: CSMP_EDIM.  w is a host array; the
+ * weights are non-negative and finite.
+ * x: the DENSE result, Float64[size(A,2)]; x_loc says where x AND b live: CSMP_HOST, or CSMP_DEVICE (the call still returns with the
+ * work done).  iterations, resnorm (||b - A z||_2 of the returned z), flags: may be NULL.  flags: CSMP_BP_CONVERGED -- both residuals
+ * passed tol at a check; CSMP_BP_FACTORED -- this call formed and factorised A A' (the first on a dictionary).
+ * Memory: G, M x M doubles, and the augmented matrix of the factorisation, (2 M)^2 doubles with M rounded up to 64 -- 128 MiB + 512 MiB
+ * at M = 4096.
+ * CSMP_EINVAL: null pointers, a b_dtype / x_loc that is neither, rho or tol not positive and finite, maxiter < 0, check_every < 1, a
+ * negative or non-finite weight, and "bp: A A' is not positive definite to working precision" (A without full row rank: a pivot of the
+ * factorisation below 4 M eps of its diagonal entry).  CSMP_EDIM: size(A,1) > size(A,2).  CSMP_ERANGE: more than 2^19 rows.
+ * CSMP_ESTATE: no dictionary -- and a host-streamed dictionary (CSMP_HOST_STREAMED), as csmp_ista.  CSMP_ENOMEM: a buffer could not be
+ * allocated; nothing of G or its factor is left behind, and the next call starts afresh. */
+#define CSMP_BP_CONVERGED 1
+#define CSMP_BP_FACTORED 2
+int csmp_bp(csmp_ctx *ctx, const void *b, int b_dtype, const double *w, int64_t nw,
+            double rho, int64_t maxiter, double tol, int64_t check_every,
+            double *x, int x_loc, int64_t *iterations, double *resnorm, int *flags);
+
+/* bp_candes / bp_ard: basispursuit_reweighting (:18-31) with csmp_bp's solve:  x = solve(w = 1);  then for i = 2 .. outer_maxiter:  w from x
+ * (scheme, eps, ard_iter: as csmp_ista_reweighted; CSMP_REWEIGHT_ARD takes supports of up to min(size(A,1), CSMP_ARD_KMAX) atoms);
+ * xs = solve(w), WARM-STARTED from the z, u, p, q of the previous solve;  norm(xs - x) < min_decrease: return xs;  else x = xs.
+ * rho, maxiter, tol, check_every: csmp_bp's, for every solve.  x, x_loc, w_out, outer_done, resnorm: as csmp_ista_reweighted.
+ * Errors: csmp_bp's and csmp_ista_reweighted's (CSMP_ERANGE: an iterate with more non-zeros than CSMP_REWEIGHT_ARD takes). */
+int csmp_bp_reweighted(csmp_ctx *ctx, const void *b, int b_dtype, int scheme, double eps, int64_t ard_iter,
+                       int64_t outer_maxiter, double min_decrease, double rho, int64_t maxiter, double tol, int64_t check_every,
+                       double *x, int x_loc, double *w_out, int64_t *outer_done, double *resnorm);
 
 /* ------------------------------------------------------------------ dictionary analysis
  * colnorms(A): src/util.jl:2.  norms[j] = ||a_j||_2 of every column of the resident dictionary, N doubles, to host memory

@@ -37,6 +37,9 @@ int csmp_bench_sweep(csmp_ctx *ctx, int variant, int reps, double *avg_ms);
  * variant 1: the yardstick -- the existing k_fr_rebuild_lds launched once per block of 128 directions on rho2 = |a_j|^2 (k_fr_colnorm2),
  * then a root kernel.  max_diff (may be NULL): max_j |w_j(fused) - w_j(split)|.  CSMP_ESTATE: no such call has been made. */
 int csmp_bench_ard_forms(csmp_ctx *ctx, int variant, int reps, double eps, double *avg_ms, double *max_diff);
+/* G = A A' of the resident dictionary by k_rowgram and its reduction alone (csmp_bp forms it once per dictionary and keeps it): M x M
+ * doubles, column-major and exactly symmetric, to host (loc = CSMP_HOST) or device memory (CSMP_DEVICE).  Nothing of the context changes. */
+int csmp_bp_rowgram(csmp_ctx *ctx, double *G_out, int loc);
 /* what configure_sweep chose for the resident dictionary: loads per unit of k_sweep_gen (16 / 8 / 4); phases the residual is
  * staged in (1: one LDS image); workgroups of a stand-alone sweep and of the sweep inside the tick kernel; dynamic LDS bytes;
  * dynamic = 1: the columns are handed out at run time (k_sweep_dyn and the DYN tick), 0: split statically; columns_per_unit: 2 or 4
@@ -57,6 +60,7 @@ int csmp_sweep_group_wide(const csmp_ctx *ctx, int *group_wide);
 #define CSMP_TUNE_PIPELINES 12    /* 1: csmp_omp_batch keeps one pipeline of three signals; 2: two pipelines side by side whatever the sizes (rounds of 3 + 3 signals, the remainder 1 + 1); 3: two pipelines of three GROUPS of signals, each group's sweeps one shared pass over A (k_sweep_multi); default 0: 3 where a shared pass serves two or more signals, else 2, from two signals and a 4-MiB dictionary on; 3 falls back to 2 where no shared sweep exists.  csmp_mp_batch: 1 keeps one stream, 2 and 3 take two whatever the size; a round with a single group runs its halves on the two streams under 2 and the whole group on one under 3 */
 #define CSMP_TUNE_GROUP_MAX 20    /* largest group of the grouped scheduler (CSMP_TUNE_PIPELINES 3); 0 = as many residual images as the LDS holds, at most 4 */
 #define CSMP_TUNE_GROUP_WIDE 21   /* 1: no wide groups (every pass serves at most group_max signals); 2: wide groups, the three of a round on ONE pipeline (a measurement: slower); default 0: batches of more signals than that run groups of up to 2 * group_max wherever the grouped scheduler has group_max = 4 images per workgroup on a Float32 dictionary and CSMP_TUNE_GROUP_MAX is 0.  CSMP_TUNE_TICK_GRID overrides the wide pass's grid too, rounded down to a multiple of 16 */
+#define CSMP_TUNE_ROWGRAM_SCALAR 22 /* 1: k_rowgram (csmp_bp, csmp_bp_rowgram) loads the dictionary with scalar loads, as for columns that start on no 16-byte boundary (the library's own copy always does: tests reach that instantiation here); the same bits */
 #define CSMP_TUNE_TICK_ORDER 10   /* 1: the tick kernel's sweep workgroups are dispatched ahead of its append stages' */
 #define CSMP_TUNE_CLAIM_POOLS 11  /* the dynamic sweep: column pools a workgroup may claim from (its own first) */
 #define CSMP_TUNE_PAIR_LDS_KIB 13 /* dynamic LDS (KiB) requested by the ticks of two pipelines side by side: above 80 = one workgroup per CU (default 81), 1 = what the kernels need */
