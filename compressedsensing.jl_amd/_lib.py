@@ -89,6 +89,10 @@ SIGNATURES = {
                           C.POINTER(C.c_int)]),
     "csmp_bp_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_double, i64, i64, C.c_double, C.c_double, i64, C.c_double, i64, vp, C.c_int, vp,
                                      C.POINTER(i64), C.POINTER(C.c_double)]),
+    "csmp_bpd": (C.c_int, [vp, vp, C.c_int, C.c_double, vp, i64, C.c_double, i64, C.c_double, i64, vp, C.c_int, C.POINTER(i64), C.POINTER(C.c_double),
+                           C.POINTER(C.c_int)]),
+    "csmp_bpd_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, i64, i64, C.c_double, C.c_double, i64, C.c_double, i64, vp, C.c_int,
+                                      vp, C.POINTER(i64), C.POINTER(C.c_double)]),
     "csmp_colnorms": (C.c_int, [vp, vp, C.c_int]),
     "csmp_cumbabel": (C.c_int, [vp, i64, C.c_int, vp, vp]),
     "csmp_sweep": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -120,6 +124,8 @@ BABEL_KMAX = 1024  # CSMP_BABEL_KMAX
 ARD_KMAX = 1024  # CSMP_ARD_KMAX
 REWEIGHT_CANDES, REWEIGHT_ARD = 0, 1  # CSMP_REWEIGHT_*
 BP_CONVERGED, BP_FACTORED = 1, 2  # CSMP_BP_*
+BPD_CONVERGED, BPD_FACTORED = 1, 2  # CSMP_BPD_*
+BPD_RHO = 100.0  # the bindings' default penalty of bpd
 
 
 def live_resources():
@@ -805,6 +811,72 @@ class Context:
         out = np.zeros((self.M, self.M), np.float64)
         self.call("csmp_bp_rowgram", ptr(out), HOST)
         return out
+
+    # ---- basis pursuit denoising
+    def _bpd_info(self, it, rn, flags):
+        return {"iterations": int(it.value), "converged": bool(flags.value & BPD_CONVERGED), "factored": bool(flags.value & BPD_FACTORED),
+                "resnorm": rn.value}
+
+    def bpd(self, b, delta, w=1.0, rho=BPD_RHO, maxiter=16384, tol=1e-8, check_every=32):
+        """csmp_bpd on a host signal: (dense z, Float64[N]; info = iterations, converged, factored, resnorm).  w: one weight or N of them.
+        The first call on a dictionary forms A Aᵀ and factorises I + A Aᵀ: (2M)² doubles of device memory (512 MiB at M = 4096) are kept until
+        the dictionary changes, apart from bp's factor."""
+        b = self._b(b)
+        w, _, _ = self._ista_args(w, None, None)
+        x = np.zeros(max(self.N, 1), np.float64)
+        rn, it, flags = C.c_double(0), i64(0), C.c_int(0)
+        self.call("csmp_bpd", ptr(b), dtype_code(b.dtype), C.c_double(delta), ptr(w), i64(len(w)), C.c_double(rho), i64(int(maxiter)),
+                  C.c_double(tol), i64(int(check_every)), ptr(x), HOST, C.byref(it), C.byref(rn), C.byref(flags))
+        return x[:self.N], self._bpd_info(it, rn, flags)
+
+    def bpd_device(self, b, delta, w, x, rho=BPD_RHO, maxiter=16384, tol=1e-8, check_every=32):
+        """torch CUDA tensors: b (M,) float32 / float64, x (N,) float64 receives the dense result.  Returns info; the work is done when the
+        call returns."""
+        import torch
+        if not (b.is_cuda and b.is_contiguous() and b.shape == (self.M,) and b.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "b must be a contiguous CUDA vector of length size(A, 1), float32 or float64")
+        if not (x.is_cuda and x.is_contiguous() and x.shape == (self.N,) and x.dtype == torch.float64):
+            raise CsmpError(EDIM, "x must be a contiguous CUDA float64 vector of length size(A, 2)")
+        w, _, _ = self._ista_args(w, None, None)
+        rn, it, flags = C.c_double(0), i64(0), C.c_int(0)
+        self.call("csmp_bpd", vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64, C.c_double(delta), ptr(w), i64(len(w)), C.c_double(rho),
+                  i64(int(maxiter)), C.c_double(tol), i64(int(check_every)), vp(x.data_ptr()), DEVICE, C.byref(it), C.byref(rn), C.byref(flags))
+        return self._bpd_info(it, rn, flags)
+
+    def bpd_reweighted(self, b, delta, scheme, eps=None, ard_iter=8, outer_maxiter=8, min_decrease=1e-4, rho=BPD_RHO, maxiter=16384, tol=1e-8,
+                       check_every=32, return_weights=False):
+        """csmp_bpd_reweighted on a host signal: (dense z, ||b - A z||, solves done[, the last weights]).  scheme: "candes" / "ard";
+        eps=None: delta for "candes", delta² for "ard" (the reference's defaults)."""
+        b = self._b(b)
+        if eps is None:
+            eps = delta if _scheme(scheme) == REWEIGHT_CANDES else delta * delta
+        x = np.zeros(max(self.N, 1), np.float64)
+        w = np.zeros(max(self.N, 1), np.float64) if return_weights else None
+        rn, done = C.c_double(0), i64(0)
+        self.call("csmp_bpd_reweighted", ptr(b), dtype_code(b.dtype), C.c_double(delta), _scheme(scheme), C.c_double(eps), i64(int(ard_iter)),
+                  i64(int(outer_maxiter)), C.c_double(min_decrease), C.c_double(rho), i64(int(maxiter)), C.c_double(tol), i64(int(check_every)),
+                  ptr(x), HOST, ptr(w), C.byref(done), C.byref(rn))
+        res = (x[:self.N], rn.value, int(done.value))
+        return res + (w[:self.N],) if return_weights else res
+
+    def bpd_reweighted_device(self, b, delta, scheme, x, w=None, eps=None, ard_iter=8, outer_maxiter=8, min_decrease=1e-4, rho=BPD_RHO,
+                              maxiter=16384, tol=1e-8, check_every=32):
+        """torch CUDA tensors: b (M,) float32 / float64; x and (optionally) w (N,) float64 receive the result and the last weights.
+        Returns (||b - A z||, solves done)."""
+        import torch
+        if not (b.is_cuda and b.is_contiguous() and b.shape == (self.M,) and b.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "b must be a contiguous CUDA vector of length size(A, 1), float32 or float64")
+        for v in (x,) if w is None else (x, w):
+            if not (v.is_cuda and v.is_contiguous() and v.shape == (self.N,) and v.dtype == torch.float64):
+                raise CsmpError(EDIM, "x and w must be contiguous CUDA float64 vectors of length size(A, 2)")
+        if eps is None:
+            eps = delta if _scheme(scheme) == REWEIGHT_CANDES else delta * delta
+        rn, done = C.c_double(0), i64(0)
+        self.call("csmp_bpd_reweighted", vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64, C.c_double(delta), _scheme(scheme),
+                  C.c_double(eps), i64(int(ard_iter)), i64(int(outer_maxiter)), C.c_double(min_decrease), C.c_double(rho), i64(int(maxiter)),
+                  C.c_double(tol), i64(int(check_every)), vp(x.data_ptr()), DEVICE, vp(w.data_ptr() if w is not None else 0), C.byref(done),
+                  C.byref(rn))
+        return rn.value, int(done.value)
 
     # ---- dictionary analysis
     def colnorms(self, device=False):

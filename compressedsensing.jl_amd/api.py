@@ -17,6 +17,7 @@ Same names, argument meaning and error behaviour as the reference (paths relativ
     argmaxinner!(P[, k])                     src/matchingpursuit.jl:181-193
     ista(A, b, λ | w[, x]; maxiter, stepsize) / fista(...) / shrinkage(x, α)   src/basispursuit.jl:144,164-204
     bp(A, b[, w]) = basispursuit / bp_candes(A, b, ε) / bp_ard(A, b, ε)         src/basispursuit.jl:1-74
+    bpd(A, b, δ[, w]) = basis_pursuit_denoising / bpd_candes(A, b, δ[, ε]) / bpd_ard(A, b, δ[, ε])   src/basispursuit.jl:76-124
     colnorms(A) / coherence(A) / babel(A, k) / cumbabel(A, k)               src/util.jl:2,96-115
 
 `A` is either a numpy matrix (uploaded to HBM for the duration of the call) or a `Dictionary`
@@ -348,6 +349,92 @@ def bp_ard(A, b, eps=1e-2, *, maxiter=8, min_decrease=1e-8, iter=8, rho=1.0, inn
     if not _is_int(iter) or iter < 1:
         raise ValueError(f"iter = {iter} has to be at least 1")
     return _bp_reweighted(A, b, "ard", eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights, int(iter))
+
+
+# ------------------------------------------------------------------------------------ basis pursuit denoising
+BPD_RHO = _lib.BPD_RHO  # the default penalty: the smallest total of the iteration table of DESIGN.md section 14
+
+
+def _bpd_knobs(A, delta, rho, maxiter, tol, check_every):
+    M, N, _ = _meta(A)
+    if not (delta >= 0 and np.isfinite(delta)):
+        raise ValueError(f"delta = {delta} has to be non-negative and finite")
+    if not (rho > 0 and np.isfinite(rho)):
+        raise ValueError(f"rho = {rho} has to be positive and finite")
+    if not (tol > 0 and np.isfinite(tol)):
+        raise ValueError(f"tol = {tol} has to be positive and finite")
+    if not maxiter >= 0:
+        raise ValueError(f"maxiter = {maxiter} has to be non-negative")
+    if not _is_int(check_every) or check_every < 1:
+        raise ValueError(f"check_every = {check_every} has to be at least 1")
+    return M, N
+
+
+def bpd(A, b, delta, w=None, *, rho=BPD_RHO, maxiter=16384, tol=1e-8, check_every=32, return_info=False):
+    """bpd(A, b, δ[, w]) = basis_pursuit_denoising (src/basispursuit.jl:76-100): min Σ w_j |x_j| subject to ‖A x − b‖₂ ≤ δ, w = ones by
+    default -- basis pursuit for data that carry noise.  Graph-form ADMM with one Cholesky factorisation of I + A Aᵀ per Dictionary (kept
+    until its dictionary changes, apart from bp's factor: (2M)² doubles of device memory, 512 MiB at M = 4096); every check_every iterations
+    the primal and dual residuals are read, and the iteration stops once both are below tol.  I + A Aᵀ is positive definite for every A:
+    more rows than columns and rank-deficient dictionaries are served.  δ = 0 is bp's problem.  Returns the exactly sparse z;
+    return_info=True: (z, info) with info = {iterations, converged, factored, resnorm = ‖b − A z‖}.  Reaching maxiter is no error
+    (converged is False)."""
+    M, N = _bpd_knobs(A, delta, rho, maxiter, tol, check_every)
+    w = np.ones(1) if w is None else np.atleast_1d(np.asarray(w, dtype=np.float64))
+    if w.ndim != 1 or len(w) not in (1, N):
+        raise ValueError(f"length(w) = {w.shape} but size(A, 2) = {N}")
+    if not np.all((w >= 0) & np.isfinite(w)):
+        raise ValueError("the weights have to be non-negative and finite")
+    D, tmp = _dict(A)
+    try:
+        xd, info = D.ctx.bpd(b, float(delta), w, float(rho), int(maxiter), float(tol), int(check_every))
+        nz = np.flatnonzero(xd)
+        x = SparseVector(N, nz, xd[nz])
+        return (x, info) if return_info else x
+    finally:
+        if tmp:
+            D.close()
+
+
+basis_pursuit_denoising = bpd
+
+
+def _bpd_reweighted(A, b, delta, scheme, eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights, ard_iter=8):
+    M, N = _bpd_knobs(A, delta, rho, inner_maxiter, tol, check_every)
+    if not (eps > 0 and np.isfinite(eps)):
+        raise ValueError(f"eps = {eps} has to be positive and finite")
+    if not _is_int(maxiter) or maxiter < 1:
+        raise ValueError(f"maxiter = {maxiter} has to be at least 1")
+    if not min_decrease >= 0:
+        raise ValueError(f"min_decrease = {min_decrease} has to be non-negative")
+    D, tmp = _dict(A)
+    try:
+        out = D.ctx.bpd_reweighted(b, float(delta), scheme, float(eps), ard_iter, int(maxiter), float(min_decrease), float(rho), int(inner_maxiter),
+                                   float(tol), int(check_every), return_weights)
+        nz = np.flatnonzero(out[0])
+        x = SparseVector(N, nz, out[0][nz])
+        return (x, out[3]) if return_weights else x
+    finally:
+        if tmp:
+            D.close()
+
+
+def bpd_candes(A, b, delta, eps=None, *, maxiter=8, min_decrease=1e-4, rho=BPD_RHO, inner_maxiter=16384, tol=1e-8, check_every=32,
+               return_weights=False):
+    """bpd_candes(A, b, δ, ε = δ; maxiter) (src/basispursuit.jl:102-121): x = bpd(A, b, δ); up to maxiter − 1 times w_j = 1 / (|x_j| + ε),
+    xs = bpd(A, b, δ, w) warm-started from the previous solve's iterates, stop once ‖xs − x‖ < min_decrease.  rho, inner_maxiter, tol,
+    check_every: bpd's, for every solve.  return_weights=True: (x, the last w)."""
+    return _bpd_reweighted(A, b, delta, "candes", delta if eps is None else eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every,
+                           return_weights)
+
+
+def bpd_ard(A, b, delta, eps=None, *, maxiter=8, min_decrease=1e-4, iter=8, rho=BPD_RHO, inner_maxiter=16384, tol=1e-8, check_every=32,
+            return_weights=False):
+    """bpd_ard(A, b, δ, ε = δ²; maxiter, iter) (src/basispursuit.jl:102-115,122-124): as bpd_candes with ard_weights!(w, A, x, ε, iter) on
+    the weights of the previous outer iteration (from ones); an iterate with more than min(size(A, 1), 1024) non-zeros is refused."""
+    if not _is_int(iter) or iter < 1:
+        raise ValueError(f"iter = {iter} has to be at least 1")
+    return _bpd_reweighted(A, b, delta, "ard", delta ** 2 if eps is None else eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every,
+                           return_weights, int(iter))
 
 
 # ------------------------------------------------------------------------------------ dictionary analysis

@@ -20,6 +20,7 @@
 #include "csmp_analysis.hpp"
 #include "csmp_reweight.hpp"
 #include "csmp_bp.hpp"
+#include "csmp_bpd.hpp"
 
 #include <algorithm>
 #include <iterator>
@@ -58,5 +59,6 @@ using namespace csmp;
 #include "host/analysis.hpp"
 #include "host/reweight.hpp"
 #include "host/bp.hpp"
+#include "host/bpd.hpp"
 #include "host/measure.hpp"
 #include "host/rccl.hpp"

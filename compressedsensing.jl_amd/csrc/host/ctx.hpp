@@ -178,6 +178,19 @@ struct BpBuf {
     bool notpd = false;     // ... and the factorisation met a pivot that is not positive to working precision
 };
 
+// basis pursuit denoising (csmp_bpd.hpp, host/bpd.hpp): the augmented matrix [K | I], K = I + A A', that the blocked Cholesky turns into R
+// beside R^-T (BpBuf's layout; R^-1 in its rows from np on) -- A A' itself is a temporary of the factorisation -- the verdict, the
+// M-vectors of the iteration and the partial sums, made on first use, sized by the dictionary: all of them, or none.  Apart from BpBuf:
+// a context may hold both factors.
+struct BpdBuf {
+    double *Gm = nullptr, *pivref = nullptr, *Dfac = nullptr, *vec = nullptr, *rpart = nullptr, *mpart = nullptr, *res = nullptr;
+    DevState* st = nullptr;
+    int M = 0, np = 0;      // rows the buffers were made for (0: none)
+    int Mp = 0;             // length of each of the eight M-vectors p, q, en, tmp, yn, v, lam, h in vec (zero beyond M: the sweep reads Mv rows)
+    bool factored = false;  // the factor belongs to the current dictionary
+    bool notpd = false;     // ... and the factorisation met a pivot that is not positive (K is positive definite: a fault, not a verdict on A)
+};
+
 struct csmp_ctx;
 // Subspace Pursuit as a resumable job: see host/gomp_sp.hpp
 struct SpJob {
@@ -285,6 +298,7 @@ struct csmp_ctx {
     AnalysisBuf analysis;
     RwBuf rw;
     BpBuf bp;
+    BpdBuf bpd;
     // profiling
     bool prof = false;
     int prof_every = 1;       // time every n-th sweep launch only (an event pair costs a few us of stream time)

@@ -248,6 +248,7 @@ static int dict_forget(csmp_ctx* ctx) {
     analysis_free(ctx->analysis);
     rw_free(ctx->rw);
     bp_free(ctx->bp);
+    bpd_free(ctx->bpd);
     return CSMP_OK;
 }
 

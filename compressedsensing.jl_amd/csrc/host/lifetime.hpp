@@ -107,6 +107,11 @@ static void bp_free(BpBuf& t) {
     t = BpBuf();
 }
 
+static void bpd_free(BpdBuf& t) {
+    dfree(t.Gm); dfree(t.pivref); dfree(t.Dfac); dfree(t.vec); dfree(t.rpart); dfree(t.mpart); dfree(t.res); dfree(t.st);
+    t = BpdBuf();
+}
+
 static void dict_release(csmp_ctx* ctx) {
     if (ctx->share && --ctx->share->refs == 0) {
         if (ctx->share->kind == 0) (void)hipFree(ctx->share->p);
@@ -133,6 +138,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     analysis_free(ctx->analysis);
     rw_free(ctx->rw);
     bp_free(ctx->bp);
+    bpd_free(ctx->bpd);
     if (ctx->comm) (void)csmp_comm_free(ctx);
     for (auto& t : ctx->twins) {
         if (t) (void)csmp_destroy(t);

@@ -186,7 +186,7 @@ fista(A::MatOrDict, b::AbstractVector, λ::Real, x::AbstractVector = spzeros(siz
 
 # ---------------------------------------------------------------------------------- reweighted l1
 # src/basispursuit.jl:18-74: candes_weights!, ard_weights! and basispursuit_reweighting with ista / fista as the solver of
-# ‖b - A x‖² + λ Σ w_j |x_j| (the loops around bp itself: bp_candes / bp_ard below; bpd needs an SOCP solver and is not part of libcsmp).
+# ‖b - A x‖² + λ Σ w_j |x_j| (the loops around bp and bpd themselves: bp_candes / bp_ard and bpd_candes / bpd_ard below).
 const CSMP_ARD_KMAX = 1024
 const CSMP_REWEIGHT_CANDES = 0
 const CSMP_REWEIGHT_ARD = 1
@@ -266,6 +266,48 @@ bp_candes(A::MatOrDict, b::AbstractVector, ε::Real = 1e-2; maxiter::Int = 8, mi
 bp_ard(A::MatOrDict, b::AbstractVector, ε::Real = 1e-2; maxiter::Int = 8, min_decrease::Real = 1e-8, iter::Int = 8, rho::Real = 1.0,
        inner_maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32, return_weights::Bool = false) =
     bp_reweighted(A, b, CSMP_REWEIGHT_ARD, ε, iter, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights)
+
+# ---------------------------------------------------------------------------------- basis pursuit denoising
+# src/basispursuit.jl:76-124: bpd(A, b, δ[, w]) = basis_pursuit_denoising -- min Σ w_j |x_j| subject to ‖A x − b‖₂ ≤ δ, by graph-form ADMM
+# with one Cholesky factorisation of I + A Aᵀ per Dictionary (csmp_bpd, include/csmp.h; no SOCP solver) -- and bpd_candes / bpd_ard,
+# bpd_reweighting around it (csmp_bpd_reweighted).  rho = 100: DESIGN.md section 14.
+const CSMP_BPD_CONVERGED = 1
+const CSMP_BPD_FACTORED = 2
+function bpd_call(A::MatOrDict, b::AbstractVector, δ::Real, w::Vector{Float64}, rho::Real, maxiter::Int, tol::Real, check_every::Int,
+                  return_info::Bool)
+    D = dict(A)
+    bb, bt = bvec(b)
+    xd = zeros(Float64, size(D, 2))
+    it, rn, flags = Ref{Int64}(0), Ref{Cdouble}(0), Ref{Cint}(0)
+    GC.@preserve bb w xd check(D, ccall((:csmp_bpd, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Ptr{Cdouble}, Int64, Cdouble, Int64, Cdouble, Int64, Ptr{Cdouble}, Cint, Ref{Int64}, Ref{Cdouble}, Ref{Cint}),
+        D.ctx, bb, bt, δ, w, length(w), rho, maxiter, tol, check_every, xd, CSMP_HOST, it, rn, flags))
+    info = (iterations = Int(it[]), converged = flags[] & CSMP_BPD_CONVERGED != 0, factored = flags[] & CSMP_BPD_FACTORED != 0, resnorm = rn[])
+    return return_info ? (sparse(xd), info) : sparse(xd)
+end
+bpd(A::MatOrDict, b::AbstractVector, δ::Real; rho::Real = 100.0, maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32,
+    return_info::Bool = false) = bpd_call(A, b, δ, Float64[1.0], rho, maxiter, tol, check_every, return_info)
+bpd(A::MatOrDict, b::AbstractVector, δ::Real, w::AbstractVector; rho::Real = 100.0, maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32,
+    return_info::Bool = false) = bpd_call(A, b, δ, convert(Vector{Float64}, w), rho, maxiter, tol, check_every, return_info)
+const basis_pursuit_denoising = bpd
+function bpd_reweighted(A::MatOrDict, b::AbstractVector, δ::Real, scheme::Integer, ε::Real, ard_iter::Int, maxiter::Int, min_decrease::Real,
+                        rho::Real, inner_maxiter::Int, tol::Real, check_every::Int, return_weights::Bool)
+    D = dict(A)
+    bb, bt = bvec(b)
+    xd, w = zeros(Float64, size(D, 2)), zeros(Float64, size(D, 2))
+    done, rn = Ref{Int64}(0), Ref{Cdouble}(0)
+    GC.@preserve bb xd w check(D, ccall((:csmp_bpd_reweighted, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cint, Cdouble, Int64, Int64, Cdouble, Cdouble, Int64, Cdouble, Int64, Ptr{Cdouble}, Cint, Ptr{Cdouble},
+         Ref{Int64}, Ref{Cdouble}),
+        D.ctx, bb, bt, δ, Cint(scheme), ε, ard_iter, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, xd, CSMP_HOST, w, done, rn))
+    return return_weights ? (sparse(xd), w) : sparse(xd)
+end
+bpd_candes(A::MatOrDict, b::AbstractVector, δ::Real, ε::Real = δ; maxiter::Int = 8, min_decrease::Real = 1e-4, rho::Real = 100.0,
+           inner_maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32, return_weights::Bool = false) =
+    bpd_reweighted(A, b, δ, CSMP_REWEIGHT_CANDES, ε, 8, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights)
+bpd_ard(A::MatOrDict, b::AbstractVector, δ::Real, ε::Real = δ^2; maxiter::Int = 8, min_decrease::Real = 1e-4, iter::Int = 8, rho::Real = 100.0,
+        inner_maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32, return_weights::Bool = false) =
+    bpd_reweighted(A, b, δ, CSMP_REWEIGHT_ARD, ε, iter, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights)
 
 # ---------------------------------------------------------------------------------- dictionary analysis
 # src/util.jl:2,96-115: colnorms, coherence, babel, cumbabel.  The inner products are raw, as in the reference (which assumes unit-norm

@@ -394,8 +394,8 @@ int csmp_ista(csmp_ctx *ctx, const void *b, int b_dtype, const double *w, int64_
 
 /* ------------------------------------------------------------------ reweighted l1
  * candes_weights! / ard_weights! / basispursuit_reweighting: src/basispursuit.jl:18-74 (bp_candes, bp_ard; bpd_candes, bpd_ard :102-124),
- * with ista / fista as the inner solver (the reference's own inner solver, bp, is csmp_bp below; bpd needs an SOCP solver and is not
- * part of this library).
+ * with ista / fista as the inner solver (the reference's own inner solvers, bp and bpd, are csmp_bp and csmp_bpd below: neither needs
+ * an LP or SOCP solver).
  *
  * ard_weights!(w, A, x, eps, iter) (:49-65): `iter` times over,  d = |x| ./ w;  K = eps I + A diag(d) A';
  * w_j = sqrt(max(a_j' K^-1 a_j, 0)) for every atom.  x, w_in, w_out: N doubles each, all three in host memory (loc = CSMP_HOST) or all
@@ -464,6 +464,50 @@ int csmp_bp(csmp_ctx *ctx, const void *b, int b_dtype, const double *w, int64_t 
 int csmp_bp_reweighted(csmp_ctx *ctx, const void *b, int b_dtype, int scheme, double eps, int64_t ard_iter,
                        int64_t outer_maxiter, double min_decrease, double rho, int64_t maxiter, double tol, int64_t check_every,
                        double *x, int x_loc, double *w_out, int64_t *outer_done, double *resnorm);
+
+/* ------------------------------------------------------------------ basis pursuit denoising
+ * basis_pursuit_denoising(A, b, delta[, w]) = bpd: src/basispursuit.jl:76-100.  min sum_j w_j |x_j| subject to ||A x - b||_2 <= delta,
+ * the form for data that carry noise -- no SOCP solver: graph-form ADMM.  Block one is (x, s) on the subspace s = A x, block two (z, v)
+ * with sum w|z| + the indicator of ||v - b|| <= delta; scaled duals u (of x = z) and lam (of s = v), penalty rho.  With
+ * K = I + A A' = R'R (formed and factorised ONCE per dictionary, kept by the context until csmp_set_dictionary; A A' itself is a
+ * temporary), shrink(t, a) = sign(t) max(|t| - a, 0), and p = A z, q = A u carried as M-vectors, one iteration is
+ *     e = v - lam - p + q;   y = K^-1 e;   c = A' y;   t = z + c;   z+ = shrink(t, w / rho);   u+ = t - z+;
+ *     r = b - A z+;   p+ = b - r;   q+ = p + (e - y) - p+                  (A A' y = (K - I) y = e - y)
+ *     h = v - y - b;   v+ = b + h min(1, delta / ||h||)  (v+ = b + h where ||h|| <= delta, ||h|| = 0 included);   lam+ = v - y - v+
+ * -- one pass over A, one over the non-zeros of z+, two triangular M x M matrix-vector products (csmp_bp has a full one besides).
+ * Start: z = u = 0, v = lam = 0.  Every check_every iterations the host reads sqrt(||u+ - u||^2 + ||lam+ - lam||^2) (primal residual)
+ * and rho sqrt(||z+ - z||^2 + ||v+ - v||^2) (dual residual) and stops when both are < tol; reaching maxiter is not an error.  The result
+ * is z: exactly sparse.  delta = 0 is allowed: the ball is the point b, and the method is another route to csmp_bp's answer.
+ * rho: unlike csmp_bp, 1 is a poor choice here; the bindings' default is 100.
+ * K is positive definite for EVERY dictionary: size(A,1) > size(A,2) and rank-deficient A, which csmp_bp refuses, are served.
+ * w, nw: nw = 1 is one weight for every atom, nw = size(A,2) one weight per atom; anything else: CSMP_EDIM.  w is a host array; the
+ * weights are non-negative and finite.
+ * x: the DENSE result, Float64[size(A,2)]; x_loc says where x AND b live: CSMP_HOST, or CSMP_DEVICE (the call still returns with the
+ * work done).  iterations, resnorm (||b - A z||_2 of the returned z), flags: may be NULL.  flags: CSMP_BPD_CONVERGED -- both residuals
+ * passed tol at a check; CSMP_BPD_FACTORED -- this call formed and factorised K (the first on a dictionary).  The factor is apart from
+ * csmp_bp's: a context may hold both, and neither call invalidates the other's.
+ * Memory: the augmented matrix of the factorisation, (2 M)^2 doubles with M rounded up to 64 -- 512 MiB at M = 4096 -- and, during the
+ * factorising call only, A A' (M x M doubles) and k_rowgram's partials.
+ * CSMP_EINVAL: null pointers, a b_dtype / x_loc that is neither, delta negative or not finite, rho or tol not positive and finite,
+ * maxiter < 0, check_every < 1, a negative or non-finite weight, and "bpd: the factorisation of I + A A' met a pivot that is not
+ * positive" (non-finite entries of A or a fault of the factorisation, never a property of a finite A).  CSMP_EDIM: nw.  CSMP_ERANGE: more
+ * than 2^19 rows.  CSMP_ESTATE: no dictionary -- and a host-streamed dictionary (CSMP_HOST_STREAMED), as csmp_ista.  CSMP_ENOMEM: a
+ * buffer could not be allocated; nothing of the factor is left behind, and the next call starts afresh. */
+#define CSMP_BPD_CONVERGED 1
+#define CSMP_BPD_FACTORED 2
+int csmp_bpd(csmp_ctx *ctx, const void *b, int b_dtype, double delta, const double *w, int64_t nw,
+             double rho, int64_t maxiter, double tol, int64_t check_every,
+             double *x, int x_loc, int64_t *iterations, double *resnorm, int *flags);
+
+/* bpd_candes / bpd_ard: bpd_reweighting (:102-124) with csmp_bpd's solve:  x = solve(w = 1);  then for i = 2 .. outer_maxiter:  w from x
+ * (scheme, eps, ard_iter: as csmp_ista_reweighted; CSMP_REWEIGHT_ARD takes supports of up to min(size(A,1), CSMP_ARD_KMAX) atoms);
+ * xs = solve(w), WARM-STARTED from the z, u, p, q, v, lam of the previous solve;  norm(xs - x) < min_decrease: return xs;  else x = xs.
+ * The reference's defaults: eps = delta (bpd_candes), eps = delta^2 (bpd_ard), min_decrease = 1e-4.
+ * delta, rho, maxiter, tol, check_every: csmp_bpd's, for every solve.  x, x_loc, w_out, outer_done, resnorm: as csmp_ista_reweighted.
+ * Errors: csmp_bpd's and csmp_ista_reweighted's (CSMP_ERANGE: an iterate with more non-zeros than CSMP_REWEIGHT_ARD takes). */
+int csmp_bpd_reweighted(csmp_ctx *ctx, const void *b, int b_dtype, double delta, int scheme, double eps, int64_t ard_iter,
+                        int64_t outer_maxiter, double min_decrease, double rho, int64_t maxiter, double tol, int64_t check_every,
+                        double *x, int x_loc, double *w_out, int64_t *outer_done, double *resnorm);
 
 /* ------------------------------------------------------------------ dictionary analysis
  * colnorms(A): src/util.jl:2.  norms[j] = ||a_j||_2 of every column of the resident dictionary, N doubles, to host memory
