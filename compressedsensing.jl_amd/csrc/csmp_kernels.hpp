@@ -2195,6 +2195,10 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
     int cslot = 0;  // pairs staged since the set of two was last written, 0 .. 31
     // the staged values of set s go out: member 2s + (lane >> 5) of a set of four, member R - 1 of the set of two
     auto cv = [&](const int i) { return mo ? p.cvec[kGroupMax + i] : p.cvec[i]; };  // (mo is 0 or kGroupMax: no indexed kernel argument)
+    // A pass whose c nobody reads (the grouped OMP scheduler's: its append stage takes the atom from the partials) gets null cvec
+    // entries, all of them (multi_members, host/omp.hpp): ONE uniform predicate, read here, under which a pair's last unit stages
+    // nothing and no c is stored.  The arg-max bookkeeping does not depend on it.
+    const bool wc = p.cvec[0] != nullptr;
     auto flush = [&](const int s) {
         double* dst;
         bool on;
@@ -2373,7 +2377,7 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
                     mine = ((lane ^ cslot) & 31) == 0;
                 }
                 const bool have = col < Ni;  // (the second column of the last pair of an odd N)
-                if (mine) {
+                if (wc && mine) {
                     cst[s] = v;
                     ccst[s] = have ? col : -1;
                 }
@@ -2385,13 +2389,15 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
             }
 #pragma unroll
             for (int i = 0; i < R; ++i) acc[0][i] = acc[1][i] = 0.0;
-            ++cslot;
-            if ((cslot & 15) == 0) {
+            if (wc) {
+                ++cslot;
+                if ((cslot & 15) == 0) {
 #pragma unroll
-                for (int s = 0; s < S4; ++s) flush(s);
-                if (cslot == 32) {
-                    if constexpr (NS > S4) flush(S4);
-                    cslot = 0;
+                    for (int s = 0; s < S4; ++s) flush(s);
+                    if (cslot == 32) {
+                        if constexpr (NS > S4) flush(S4);
+                        cslot = 0;
+                    }
                 }
             }
             cb = 0;
@@ -2414,8 +2420,10 @@ __device__ __forceinline__ void sweep_body_multi(const MultiSweep<TA>& p, const 
             if (ileft > 0) issue(buf[d]);
         }
     }
+    if (wc) {
 #pragma unroll
-    for (int s = 0; s < NS; ++s) flush(s);
+        for (int s = 0; s < NS; ++s) flush(s);
+    }
     // member i's 4 NW partials, the layout argmax_reduce reads: a member of a set of four has ONE row per column parity and wave,
     // so each of its two rows fills two of the wave's four entries (a repeated entry never wins better() against its twin);
     // better() then orders the two parities as it orders the waves: larger value, then the LOWER index
@@ -2497,6 +2505,7 @@ __device__ __forceinline__ void sweep_body_multi_w4(const MultiSweep<TA>& p, con
     }
     CStage<R> cs;
     cs.init();
+    const bool wc = p.cvec[0] != nullptr;  // (sweep_body_multi: a pass whose c nobody reads stages and stores none)
     int64_t icol = col0, ccol = col0;
     int ib = 0, cb = 0;
     const int64_t T = ncol * nunit;
@@ -2569,7 +2578,7 @@ __device__ __forceinline__ void sweep_body_multi_w4(const MultiSweep<TA>& p, con
 #pragma unroll
             for (int i = 0; i < R; ++i) {
                 const double c = wave_xsum(acc[i]);
-                cs.put(lane, i, c);
+                if (wc) cs.put(lane, i, c);
                 const double av = fabs(c);
                 if (av > bestv[i]) {  // columns arrive in increasing order: '>' keeps the first maximum
                     bestv[i] = av;
@@ -2577,8 +2586,10 @@ __device__ __forceinline__ void sweep_body_multi_w4(const MultiSweep<TA>& p, con
                 }
                 acc[i] = 0.0;
             }
-            cs.col(lane, ccol);
-            cs.next(1, p.cvec, live);
+            if (wc) {
+                cs.col(lane, ccol);
+                cs.next(1, p.cvec, live);
+            }
             cb = 0;
             ccol += stride;
         }
@@ -2602,7 +2613,7 @@ __device__ __forceinline__ void sweep_body_multi_w4(const MultiSweep<TA>& p, con
             if (ileft > 0) issue(buf[d]);
         }
     }
-    cs.flush(p.cvec, live);
+    if (wc) cs.flush(p.cvec, live);
 #pragma unroll
     for (int i = 0; i < R; ++i) argmax_put_rows(redv + i * 4 * NW, redi + i * 4 * NW, wave, lane, bestv[i], besti[i]);
     __syncthreads();

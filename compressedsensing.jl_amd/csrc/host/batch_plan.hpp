@@ -2,6 +2,7 @@
 // rounds a batch runs in (host/forward.hpp: batch_impl).  Plain C++, no HIP: included by csmp.hip (the library) and, alone, by
 // tools/sanitize/hostonly_driver.cpp, which checks every plan a batch of up to 64 signals can get.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -55,10 +56,39 @@ static std::vector<PlanGroup> even_groups(int64_t nsig, int R) {
     return groups;
 }
 
+// The groups of WIDE passes (R members in two halves of up to `narrow`, R >= 2 narrow: every group before the last stays wide): ceil(nsig / R) groups as even_groups has them,
+// consecutive signals, the larger first -- but where the last group can be cut to `narrow` signals without another pass it is, and
+// runs the narrow pass, which costs 35-45 us less than a wide one at 4096 x 65536 f32 whatever the wide one's halves hold (DESIGN.md
+// section 0.3, rounds 15 and 17); the other groups take the rest, full ones first, then one group with what is left:
+//   p = ceil(nsig / R) >= 2 and nsig <= R (p - 1) + narrow:  R, ..., R, nsig - narrow - R (p - 2), narrow    (the rest is even: even_groups)
+//   R = 8, narrow = 4:  9: 5 + 4   10: 6 + 4   12: 8 + 4   17: 8 + 5 + 4   18: 8 + 6 + 4   20: 8 + 8 + 4;  13 .. 16, 21 .. 24: even
+// split: 0 this rule; 1 even_groups (the A/B switch, csmp_tune group_split); 2 and 3 are measurements of the rule's neighbours where it
+// applies -- 2: the groups before the narrow one even (18: 7 + 7 + 4), 3: full groups, then what is left (18: 8 + 8 + 2).
+// Measured on the benchmark (4096 x 65536 f32, k = 256), atoms/s of a whole call, medians, this rule / even: 18 signals 29 352 / 28 162
+// (8 + 8 + 2: 29 109, 7 + 7 + 4: 28 717, one reading each), 20: 32 655 / 30 909, 10: 27 374 / 24 540, 12: 31 554 / 29 180,
+// 17: 28 422 / 27 260, 25: 31 059 / 30 078.  The narrow group on B instead (A: 8, 6; B: 4) read x 1.007 / 1.005 at
+// 18 / 20 signals, about the parent's run-to-run spread: not adopted.  Not measured: every other size.
+static std::vector<PlanGroup> narrow_last_groups(int64_t nsig, int R, int narrow, int split = 0) {
+    if (nsig < 1 || R < 1) return {};
+    const int64_t p = (nsig + R - 1) / R;
+    if (split == 1 || narrow < 1 || 2 * narrow > R || p < 2 || nsig > (int64_t)R * (p - 1) + narrow) return even_groups(nsig, R);
+    std::vector<PlanGroup> groups;
+    if (split == 2) {
+        groups = even_groups(nsig - narrow, R);
+    } else {
+        const int64_t last = split == 3 ? nsig - (int64_t)R * (p - 1) : narrow;
+        for (int64_t at = 0, left = nsig - last; left > 0; at += R, left -= R) groups.push_back({at, (int)(left < R ? left : R)});
+        if (split == 3) narrow = (int)last;
+    }
+    groups.push_back({nsig - narrow, narrow});
+    return groups;
+}
+
 // The rounds of a batch of nsig signals (R: the members a shared pass serves, ctx->sweep_group or ctx->group_wide).  Pairs: rounds of 3 + 3 while six or
-// more signals remain, then 1 + 1, then a lone signal in the one-pipeline form.  Grouped: the fewest shared passes (even_groups)
+// more signals remain, then 1 + 1, then a lone signal in the one-pipeline form.  Grouped: the fewest shared passes (even_groups; wide
+// groups, narrow > 0: narrow_last_groups with that half and split)
 // dealt six to a round, even offsets to A and odd ones to B; a last round may leave B with no group and keeps the pair form.
-static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int R, bool one_pipe = false) {
+static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int R, bool one_pipe = false, int narrow = 0, int split = 0) {
     std::vector<PlanRound> rounds;
     auto round = [&](RoundForm form) -> PlanRound& {
         rounds.emplace_back();
@@ -94,7 +124,7 @@ static std::vector<PlanRound> batch_plan(int64_t nsig, BatchSchedule sched, int 
             if (at < nsig) round(RoundForm::One).g[0][0] = {at, 1};
             break;
         case BatchSchedule::Grouped: {
-            const std::vector<PlanGroup> groups = even_groups(nsig, R);
+            const std::vector<PlanGroup> groups = narrow > 0 ? narrow_last_groups(nsig, R, narrow, split) : even_groups(nsig, R);
             for (size_t i = 0; i < groups.size(); ++i) {
                 const size_t per = one_pipe ? 3 : 6;  // (one_pipe, a measurement: three groups to a round, all on A; B stays empty)
                 if (i % per == 0) round(RoundForm::Grouped);

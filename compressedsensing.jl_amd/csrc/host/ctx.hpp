@@ -263,6 +263,8 @@ struct csmp_ctx {
     int tune_rebuild_direct = 0;  // csmp_tune: the oblivious start's Q'A pass reads its directions from L2 (k_fr_rebuild) instead of the LDS
     int tune_swap_refuse = 0;  // csmp_tune: OMPR's inverse-Gram exchanges fail their guard (tests walk the fallback to the QR path)
     int tune_rowgram_scalar = 0;  // csmp_tune: k_rowgram without 16-byte loads
+    int tune_pass_c = 0;      // csmp_tune: 1 = the grouped OMP scheduler's passes store c, which nothing reads (shared_pass_launch)
+    int tune_group_split = 0; // csmp_tune: how the grouped scheduler cuts a batch into wide groups, narrow_last_groups' split (1 = evenly)
     int tune_diag_split = 0;  // csmp_tune: fused kernels run as one launch per part (a kernel trace then shows the parts)
     int64_t tune_batch_budget_mib = 0;  // csmp_tune: HBM the batched path's per-signal state may take (MiB), 0 = what is free  // csmp_tune (include/csmp_internal.h): measurement overrides, 0 = automatic
     // options (csmp_set_option, include/csmp.h)

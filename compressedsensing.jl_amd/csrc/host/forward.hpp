@@ -403,7 +403,9 @@ static int batch_impl(csmp_ctx* ctx, BatchIO& io, bool isfr, double eps, double 
         // atoms/s at 18 / 20 signals, two runs each: 2 + 1 on 256 workgroups 26 087, 26 176 / 27 622, 27 735; three groups on ONE pipeline
         // (csmp_tune group_wide 2) 25 257, 25 071 / 26 958, 27 060 -- its append launches have no other pipeline's sweep to run under.
         const int members = wide ? ctx->group_wide : ctx->sweep_group;
-        for (const PlanRound& r : batch_plan(nsig, sched, members, wide && ctx->tune_group_wide == 2)) {
+        // ... and end on a group of sweep_group signals, a narrow pass, where that costs no pass more (narrow_last_groups, host/batch_plan.hpp;
+        // 18 signals: 8 + 6 + 4, the 8 and the 4 on A, the 6 on B)
+        for (const PlanRound& r : batch_plan(nsig, sched, members, wide && ctx->tune_group_wide == 2, wide ? ctx->sweep_group : 0, ctx->tune_group_split)) {
             CHECK(each_member(r, init));
             CHECK(ctx->dtype == CSMP_F32 ? run_round<float>(r, ctx, tw, isfr, k, eps, p2) : run_round<double>(r, ctx, tw, isfr, k, eps, p2));
             CHECK(finish_round(r));

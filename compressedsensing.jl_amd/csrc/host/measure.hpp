@@ -126,9 +126,13 @@ extern "C" int csmp_live_resources(int64_t* device_bytes, int64_t* device_blocks
 // csmp_bench_sweep's variants 1 .. 3: the grouped scheduler's passes alone, back to back on one stream, as it launches them (grid,
 // LDS request of one workgroup per CU) on slots filled with the pseudo-random residual -- 1: the narrow pass (k_sweep_multi,
 // sweep_group members, kGroupTickGrid); 2: the wide pass (k_sweep_wide, twice sweep_group members, kWideTickGrid), nontemporal loads;
-// 3: the wide pass with default-policy loads.  csmp_tune's group_max and tick_grid set the members and the grid.
+// 3: the wide pass with default-policy loads, what the scheduler runs.  1 .. 3 store every member's c, as csmp_mp_batch's passes do;
+// 4 and 5 are 1 and 3 WITHOUT c stores, the passes of the grouped OMP scheduler.  csmp_tune's group_max and tick_grid set the
+// members and the grid.
 template <typename TA>
 static int bench_shared_sweep(csmp_ctx* ctx, int variant, int reps, double* avg_ms) {
+    const bool need_c = variant <= 3;
+    if (!need_c) variant = variant == 4 ? 1 : 3;
     const int R = ctx->sweep_group, wide = variant >= 2;
     if (R < 1) return fail(ctx, CSMP_ESTATE, "bench_sweep: no shared sweep for this dictionary");
     if (wide && ctx->dtype != CSMP_F32) return fail(ctx, CSMP_ESTATE, "bench_sweep: the wide pass serves Float32 dictionaries");
@@ -152,7 +156,7 @@ static int bench_shared_sweep(csmp_ctx* ctx, int variant, int reps, double* avg_
     p.A = (const TA*)ctx->dA; p.ld = ctx->ld; p.Mv = ctx->Mv; p.N = ctx->N;
     p.eps = 0.0; p.check_eps = 0; p.skipmask = 0; p.KP = ctx->sweep_KP;
     p.nblk = wide ? wide_nblk(ctx) : pipe_nblk(ctx, ctx->dtype == CSMP_F32 ? kGroupTickGrid : kPairTickGrid);
-    multi_members<TA>(ctx, p, 0, members);
+    multi_members<TA>(ctx, p, 0, members, need_c);
     const size_t lds = std::max(sweep_multi_lds_bytes(p.KP, p.n), (size_t)kPairLdsKiB * 1024);
     auto launch = [&]() -> hipError_t { return wide ? wide_launch<TA>(ctx, p, lds, variant == 2) : multi_launch<TA>(ctx, p, lds); };
     for (int i = 0; i < 3; ++i) HIPCHECK(launch());
@@ -175,7 +179,7 @@ static int bench_shared_sweep(csmp_ctx* ctx, int variant, int reps, double* avg_
 extern "C" int csmp_bench_sweep(csmp_ctx* ctx, int variant, int reps, double* avg_ms) {
     if (!ctx || reps < 1) return CSMP_EINVAL;
     if (!ctx->dA) return fail(ctx, CSMP_ESTATE, "no dictionary set (csmp_set_dictionary)");
-    if (variant < 0 || variant > 3) return fail(ctx, CSMP_ESTATE, "bench_sweep: variant 0 (the product kernel), 1 (the shared pass), 2 (the wide pass) or 3 (the wide pass, default-policy loads)");
+    if (variant < 0 || variant > 5) return fail(ctx, CSMP_ESTATE, "bench_sweep: variant 0 (the product kernel), 1 (the shared pass), 2 (the wide pass), 3 (the wide pass, default-policy loads), 4 or 5 (1 or 3 without c stores)");
     HIPCHECK(hipSetDevice(ctx->dev));
     if (variant != 0) return ctx->dtype == CSMP_F32 ? bench_shared_sweep<float>(ctx, variant, reps, avg_ms) : bench_shared_sweep<double>(ctx, variant, reps, avg_ms);
     CHECK(solver_ensure(ctx, 1, 1, false));
@@ -268,6 +272,11 @@ extern "C" int csmp_tune(csmp_ctx* ctx, int key, int64_t value) {
         case CSMP_TUNE_PAIR_SPLIT: ctx->tune_pair_split = value == 1 ? 1 : 0; return CSMP_OK;
         case CSMP_TUNE_FAIL_ALLOC: ctx->tune_fail_alloc = (int)value; return CSMP_OK;
         case CSMP_TUNE_ROWGRAM_SCALAR: ctx->tune_rowgram_scalar = value == 1 ? 1 : 0; return CSMP_OK;
+        case CSMP_TUNE_PASS_C: ctx->tune_pass_c = value == 1 ? 1 : 0; return CSMP_OK;
+        case CSMP_TUNE_GROUP_SPLIT:
+            if (value > 3) return fail(ctx, CSMP_EINVAL, "csmp_tune: group_split must be 0 (a narrow last group where it costs no pass), 1 (even), 2 or 3 (measurements)");
+            ctx->tune_group_split = (int)value;
+            return CSMP_OK;
         case CSMP_TUNE_GROUP_MAX:
             if (value > kGroupMax) return fail(ctx, CSMP_EINVAL, "csmp_tune: group_max must be 0 (what the LDS holds) or 1 .. 4");
             ctx->tune_group_max = (int)value;

@@ -19,7 +19,7 @@
 constexpr bool kMpSplitLone = false;
 template <typename TA>
 static int mp_group_step(csmp_ctx* ctx, int size, int nblk, int nblk_wide, size_t lds_sweep) {
-    CHECK(shared_pass_launch<TA>(ctx, 0, size, 0.0, 0, 0, nblk, nblk_wide, lds_sweep));  // (eps, check_eps, skipmask: MP never stops early)
+    CHECK(shared_pass_launch<TA>(ctx, 0, size, 0.0, 0, 0, nblk, nblk_wide, lds_sweep, true));  // (eps, check_eps, skipmask: MP never stops early; need_c: k_mp_group reads c)
     const bool wide = size > kGroupMax;
     MpGroup g;
     g.n = size;

@@ -205,9 +205,10 @@ static hipError_t wide_launch(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t lds
 }
 // the members [first, first + size) step 3 of the slots from slot0 as a pass's entries: up to kGroupMax of them the narrow pass's
 // [0, n); more, the wide pass's halves [0, n) and [kGroupMax, kGroupMax + n1).  Entries past a half's members repeat its last one
-// (the narrow pass never reads them; the wide pass stages their image and masks them).
+// (the narrow pass never reads them; the wide pass stages their image and masks them).  need_c false: EVERY cvec entry null -- the
+// pass stages and stores no c (sweep_body_multi, sweep_body_multi_w4).
 template <typename TA>
-static void multi_members(csmp_ctx* ctx, MultiSweep<TA>& p, int slot0, int size) {
+static void multi_members(csmp_ctx* ctx, MultiSweep<TA>& p, int slot0, int size, bool need_c) {
     const bool wide = size > kGroupMax;
     p.n = wide ? (size + 1) / 2 : size;
     p.n1 = wide ? size / 2 : 0;
@@ -215,7 +216,7 @@ static void multi_members(csmp_ctx* ctx, MultiSweep<TA>& p, int slot0, int size)
         const int h = e / kGroupMax, i = e % kGroupMax;
         const int m = h == 0 || !wide ? std::min(i, p.n - 1) : p.n + std::min(i, p.n1 - 1);
         const Solver& s = *slot_ptr(ctx, slot0 + 3 * m);
-        p.r[e] = s.r; p.cvec[e] = s.cvec; p.pval[e] = s.pval; p.pidx[e] = s.pidx; p.st[e] = s.st;
+        p.r[e] = s.r; p.cvec[e] = need_c ? s.cvec : nullptr; p.pval[e] = s.pval; p.pidx[e] = s.pidx; p.st[e] = s.st;
     }
 }
 // Float32: the 512-thread pair body, whose unit is its own (4 loads per column); Float64: the four-wave body on ctx->sweep_U
@@ -233,15 +234,18 @@ static hipError_t multi_launch(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t ld
 // The shared pass of a group: the `size` members in the slots slot0, slot0 + 3, ... sweep in ONE launch that reads A once for all of
 // them -- the narrow pass on nblk workgroups, for more than kGroupMax members (more than a workgroup has images) the wide pass on
 // nblk_wide, two workgroups per read of A -- under an LDS request of at least lds_sweep.  group_pipe_launch's sweep stage and a
-// step of csmp_mp_batch's groups (mp_group_step, host/mp_batch.hpp).
+// step of csmp_mp_batch's groups (mp_group_step, host/mp_batch.hpp).  need_c: the pass writes every member's c = A'r to its slot's
+// cvec.  k_mp_group reads c there; the grouped OMP scheduler's append stage (k_append_group: qr1_body) takes its atom from the
+// pass's partials and k_finish_group reads R, z and the selection, so its passes store none (2.4 GB a call of 18 signals, k = 256, at
+// N = 65536) unless csmp_tune pass_c asks for them.
 template <typename TA>
 static int shared_pass_launch(csmp_ctx* ctx, int slot0, int size, double eps, int check_eps, int skipmask, int nblk, int nblk_wide,
-                              size_t lds_sweep) {
+                              size_t lds_sweep, bool need_c) {
     MultiSweep<TA> p;
     p.A = (const TA*)ctx->dA; p.ld = ctx->ld; p.Mv = ctx->Mv; p.N = ctx->N;
     const bool wide = size > kGroupMax;
     p.eps = eps; p.check_eps = check_eps; p.skipmask = skipmask; p.nblk = wide ? nblk_wide : nblk; p.KP = ctx->sweep_KP;
-    multi_members<TA>(ctx, p, slot0, size);
+    multi_members<TA>(ctx, p, slot0, size, need_c);
     // ONE sampled launch per shared pass: it reads A once, whatever the group size
     const bool timed = prof_pick(ctx);
     if (timed) CHECK(prof_mark(ctx));
@@ -274,7 +278,8 @@ static int group_pipe_launch(Pipe& gp, int64_t n) {
         hipLaunchKernelGGL(kern, dim3((a.n1 + a.n2) * G), dim3(kSweepThreads), gp.lds, ctx->stream, a, G);
         HIPCHECK(hipGetLastError());
     }
-    if (t.az) CHECK(shared_pass_launch<TA>(ctx, t.z, gp.size[t.z], gp.eps, t.tz > 0 ? 1 : 0, skip, gp.nblk, gp.nblk_wide, gp.lds_sweep));
+    if (t.az) CHECK(shared_pass_launch<TA>(ctx, t.z, gp.size[t.z], gp.eps, t.tz > 0 ? 1 : 0, skip, gp.nblk, gp.nblk_wide, gp.lds_sweep,
+                                          ctx->tune_pass_c == 1));
     return CSMP_OK;
 }
 

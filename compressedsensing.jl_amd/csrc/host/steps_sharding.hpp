@@ -95,6 +95,7 @@ static void copy_options(csmp_ctx* dst, const csmp_ctx* src) {
     dst->tick_nblk = src->tick_nblk;
     dst->tune_swap_refuse = src->tune_swap_refuse;
     dst->tune_rebuild_direct = src->tune_rebuild_direct;
+    dst->tune_pass_c = src->tune_pass_c;  // (pipeline B's passes are launched from the twin: group_pipe_launch)
 }
 extern "C" int csmp_clone(csmp_ctx* src, csmp_ctx** out) {
     if (!src || !out) return CSMP_EINVAL;

@@ -30,7 +30,8 @@ int csmp_live_resources(int64_t *device_bytes, int64_t *device_blocks, int64_t *
  * bracketed by one HIP event pair on the ctx stream; returns the average ms per sweep.  variant 0: the product kernel.  Variants
  * 1 .. 3 time the passes of csmp_omp_batch's grouped scheduler alone, as it launches them -- 1: the shared pass of group_max residuals
  * (k_sweep_multi); 2: the wide pass of 2 * group_max residuals (k_sweep_wide, Float32), nontemporal loads; 3: the wide pass with
- * default-policy loads.  CSMP_TUNE_GROUP_MAX and CSMP_TUNE_TICK_GRID set their members and grid. */
+ * default-policy loads (what the scheduler runs).  1 .. 3 store every member's c; 4 and 5 are 1 and 3 without c stores, as csmp_omp_batch's
+ * grouped scheduler launches them.  CSMP_TUNE_GROUP_MAX and CSMP_TUNE_TICK_GRID set their members and grid. */
 int csmp_bench_sweep(csmp_ctx *ctx, int variant, int reps, double *avg_ms);
 /* the N-pass of csmp_ard_weights alone, on the directions W = A_S L^-T the LAST csmp_ard_weights call of this context left behind (k of
  * them): `reps` runs bracketed by one HIP event pair, the average ms of one.  variant 0: k_ard_forms, the fused kernel the library runs.
@@ -61,6 +62,8 @@ int csmp_sweep_group_wide(const csmp_ctx *ctx, int *group_wide);
 #define CSMP_TUNE_GROUP_MAX 20    /* largest group of the grouped scheduler (CSMP_TUNE_PIPELINES 3); 0 = as many residual images as the LDS holds, at most 4 */
 #define CSMP_TUNE_GROUP_WIDE 21   /* 1: no wide groups (every pass serves at most group_max signals); 2: wide groups, the three of a round on ONE pipeline (a measurement: slower); default 0: batches of more signals than that run groups of up to 2 * group_max wherever the grouped scheduler has group_max = 4 images per workgroup on a Float32 dictionary and CSMP_TUNE_GROUP_MAX is 0.  CSMP_TUNE_TICK_GRID overrides the wide pass's grid too, rounded down to a multiple of 16 */
 #define CSMP_TUNE_ROWGRAM_SCALAR 22 /* 1: k_rowgram (csmp_bp, csmp_bp_rowgram) loads the dictionary with scalar loads, as for columns that start on no 16-byte boundary (the library's own copy always does: tests reach that instantiation here); the same bits */
+#define CSMP_TUNE_PASS_C 23       /* 1: the shared passes of csmp_omp_batch's grouped scheduler store every member's c = A'r, which nothing reads there; default 0: they store none (csmp_mp_batch's passes always do).  The same results */
+#define CSMP_TUNE_GROUP_SPLIT 24  /* how the grouped scheduler cuts a batch into WIDE groups (host/batch_plan.hpp: narrow_last_groups).  Default 0: ceil(nsig / group_wide) groups, the last one of group_max signals -- a narrow pass -- where that takes no pass more (18 signals: 8 + 6 + 4); 1: as even as possible (6 + 6 + 6); 2, 3: measurements (7 + 7 + 4, 8 + 8 + 2).  The same results */
 #define CSMP_TUNE_TICK_ORDER 10   /* 1: the tick kernel's sweep workgroups are dispatched ahead of its append stages' */
 #define CSMP_TUNE_CLAIM_POOLS 11  /* the dynamic sweep: column pools a workgroup may claim from (its own first) */
 #define CSMP_TUNE_PAIR_LDS_KIB 13 /* dynamic LDS (KiB) requested by the ticks of two pipelines side by side: above 80 = one workgroup per CU (default 81), 1 = what the kernels need */

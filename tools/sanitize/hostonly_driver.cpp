@@ -185,14 +185,19 @@ static void batch_plans() {
     const int kSlots = 3 * 8;
     for (int64_t nsig = 1; nsig <= 64; ++nsig)
         for (int R = 1; R <= 8; ++R)
-            for (BatchSchedule sched : {BatchSchedule::Signals, BatchSchedule::One, BatchSchedule::Pairs, BatchSchedule::Grouped}) {
-                const std::vector<PlanRound> plan = batch_plan(nsig, sched, R);
+            for (BatchSchedule sched : {BatchSchedule::Signals, BatchSchedule::One, BatchSchedule::Pairs, BatchSchedule::Grouped})
+              // the grouped schedule's split (narrow_last_groups): narrow 0 and split 1 are the even split, as is every R < 2 narrow; split 0
+              // the rule, 2 and 3 its measured neighbours
+              for (int mode = 0; mode < (sched == BatchSchedule::Grouped ? 5 : 1); ++mode) {
+                const int narrow = mode == 0 ? 0 : 4, split = mode == 0 ? 0 : mode - 1;
+                const std::vector<PlanRound> plan = batch_plan(nsig, sched, R, false, narrow, split);
                 if (sched == BatchSchedule::Signals) {
                     EXPECT(plan.empty());
                     continue;
                 }
                 std::vector<int> seen((size_t)nsig, 0);
                 int64_t next = 0;  // signals are dealt in order: A's groups, then B's, within a round
+                int prev_size = 0;
                 const int64_t ngroups = (nsig + R - 1) / R;
                 for (size_t j = 0; j < plan.size(); ++j) {
                     const PlanRound& r = plan[j];
@@ -233,10 +238,25 @@ static void batch_plans() {
                         EXPECT(r.form == RoundForm::Grouped);
                         const int64_t in_round = std::min<int64_t>(6, ngroups - 6 * (int64_t)j);
                         EXPECT(live[0] == (int)(in_round + 1) / 2 && live[1] == (int)in_round / 2);
+                        // the rule applies to wide groups where the last one can be cut to `narrow` signals without another pass; then
+                        // every group before the last is a wide one (more than `narrow` members), split 0: full groups, one with the
+                        // rest, and `narrow`; split 2: the groups before the last within one of each other; split 3: full groups, the rest
+                        const bool ruled = narrow > 0 && R >= 2 * narrow && split != 1 && ngroups >= 2 && nsig <= (int64_t)R * (ngroups - 1) + narrow;
                         for (int64_t i = 0; i < in_round; ++i) {
                             const PlanGroup& G = r.g[i % 2][i / 2];
                             const int64_t gi = 6 * (int64_t)j + i;
-                            EXPECT(G.first == next && G.size == (int)(nsig / ngroups + (gi < nsig % ngroups ? 1 : 0)) && G.size <= R);
+                            int want = (int)(nsig / ngroups + (gi < nsig % ngroups ? 1 : 0));
+                            if (ruled) {
+                                const int64_t last = split == 3 ? nsig - (int64_t)R * (ngroups - 1) : narrow, rest = nsig - last;
+                                const int64_t before = ngroups - 1;
+                                if (gi == before) want = (int)last;
+                                else if (split == 2) want = (int)(rest / before + (gi < rest % before ? 1 : 0));
+                                else want = (int)std::min<int64_t>(R, rest - R * gi);
+                                if (gi < before) EXPECT(G.size > narrow);
+                            }
+                            EXPECT(G.first == next && G.size == want && G.size >= 1 && G.size <= R);
+                            if (gi > 0) EXPECT(G.size <= prev_size);  // the larger first
+                            prev_size = G.size;
                             next += G.size;
                         }
                         continue;
@@ -246,7 +266,11 @@ static void batch_plans() {
                 EXPECT(next == nsig);
                 if (sched == BatchSchedule::Grouped) EXPECT((int64_t)plan.size() == (ngroups + 5) / 6);
                 for (int64_t s = 0; s < nsig; ++s) EXPECT(seen[(size_t)s] == 1);
-            }
+              }
+    const int want18[3] = {8, 6, 4}, want20[3] = {8, 8, 4};
+    const std::vector<PlanGroup> g18 = narrow_last_groups(18, 8, 4), g20 = narrow_last_groups(20, 8, 4);
+    EXPECT(g18.size() == 3 && g20.size() == 3);
+    for (size_t i = 0; i < 3 && g18.size() == 3 && g20.size() == 3; ++i) EXPECT(g18[i].size == want18[i] && g20[i].size == want20[i]);
 }
 
 // every plan csmp_mp_batch can get for nsig 1..64 (host/batch_plan.hpp: mp_batch_plan): each signal in exactly one group, the groups
