@@ -93,6 +93,7 @@ SIGNATURES = {
                            C.POINTER(C.c_int)]),
     "csmp_bpd_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, i64, i64, C.c_double, C.c_double, i64, C.c_double, i64, vp, C.c_int,
                                       vp, C.POINTER(i64), C.POINTER(C.c_double)]),
+    "csmp_sbl": (C.c_int, [vp, vp, C.c_int, C.c_double, i64, C.c_double, vp, vp, vp, C.c_int, C.POINTER(i64), C.POINTER(C.c_int)]),
     "csmp_colnorms": (C.c_int, [vp, vp, C.c_int]),
     "csmp_cumbabel": (C.c_int, [vp, i64, C.c_int, vp, vp]),
     "csmp_sweep": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -107,6 +108,9 @@ INTERNAL_SIGNATURES = {
     "csmp_bench_sweep": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "csmp_bench_ard_forms": (C.c_int, [vp, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "csmp_bp_rowgram": (C.c_int, [vp, vp, C.c_int]),
+    "csmp_sbl_rowgram": (C.c_int, [vp, vp, vp, C.c_int]),
+    "csmp_sbl_forms": (C.c_int, [vp, vp, i64, vp, vp, vp, C.c_int]),
+    "csmp_bench_sbl": (C.c_int, [vp, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "csmp_profile_overhead": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
     "csmp_live_resources": (C.c_int, [C.POINTER(i64)] * 6),
     "csmp_profile_window": (C.c_int, [vp, C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
@@ -117,7 +121,7 @@ INTERNAL_SIGNATURES = {
     "csmp_batch_layout": (C.c_int, [vp, C.POINTER(i64), C.POINTER(C.c_int)]),
     "csmp_batch_screen_kernel": (C.c_char_p, [vp]),
 }
-TUNE = {"sweep_grid": 2, "sweep_unit": 3, "tick_grid": 4, "batch_budget_mib": 5, "diag_split": 6, "swap_refuse": 7, "rebuild_direct": 8, "sweep_dyn": 9, "tick_order": 10, "claim_pools": 11, "pipelines": 12, "pair_lds_kib": 13, "pair_split": 14, "sweep_lds_kib": 15, "sweep_short": 16, "phase_rows": 17, "fail_alloc": 18, "screen_static": 19, "group_max": 20, "group_wide": 21, "rowgram_scalar": 22, "pass_c": 23, "group_split": 24}  # CSMP_TUNE_* (include/csmp_internal.h)
+TUNE = {"sweep_grid": 2, "sweep_unit": 3, "tick_grid": 4, "batch_budget_mib": 5, "diag_split": 6, "swap_refuse": 7, "rebuild_direct": 8, "sweep_dyn": 9, "tick_order": 10, "claim_pools": 11, "pipelines": 12, "pair_lds_kib": 13, "pair_split": 14, "sweep_lds_kib": 15, "sweep_short": 16, "phase_rows": 17, "fail_alloc": 18, "screen_static": 19, "group_max": 20, "group_wide": 21, "rowgram_scalar": 22, "pass_c": 23, "group_split": 24, "sbl_scalar": 25}  # CSMP_TUNE_* (include/csmp_internal.h)
 
 COMM_ID_BYTES = 128  # CSMP_COMM_ID_BYTES
 BABEL_KMAX = 1024  # CSMP_BABEL_KMAX
@@ -126,6 +130,7 @@ REWEIGHT_CANDES, REWEIGHT_ARD = 0, 1  # CSMP_REWEIGHT_*
 BP_CONVERGED, BP_FACTORED = 1, 2  # CSMP_BP_*
 BPD_CONVERGED, BPD_FACTORED = 1, 2  # CSMP_BPD_*
 BPD_RHO = 100.0  # the bindings' default penalty of bpd
+SBL_CONVERGED = 1  # CSMP_SBL_*
 
 
 def live_resources():
@@ -877,6 +882,79 @@ class Context:
                   C.c_double(tol), i64(int(check_every)), vp(x.data_ptr()), DEVICE, vp(w.data_ptr() if w is not None else 0), C.byref(done),
                   C.byref(rn))
         return rn.value, int(done.value)
+
+    # ---- sparse Bayesian learning
+    def sbl(self, b, sigma2, maxiter=None, min_change=1e-6, gamma=None, return_gamma=False):
+        """csmp_sbl on a host signal: (dense x, Float64[N]; info = iterations, converged[; the last gamma]).  maxiter=None: 128 N, the
+        reference's default.  gamma: the N variances to start from (None: ones).  The first call on a dictionary allocates the factor's
+        (2M)² doubles, two M x M matrices and four N-vectors of device memory, kept until the dictionary changes."""
+        b = self._b(b)
+        if gamma is not None:
+            gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+            if gamma.shape != (self.N,):
+                raise CsmpError(EDIM, "length(gamma) has to be size(A, 2)")
+        x = np.zeros(max(self.N, 1), np.float64)
+        g = np.zeros(max(self.N, 1), np.float64) if return_gamma else None
+        it, flags = i64(0), C.c_int(0)
+        self.call("csmp_sbl", ptr(b), dtype_code(b.dtype), C.c_double(sigma2), i64(128 * self.N if maxiter is None else int(maxiter)),
+                  C.c_double(min_change), ptr(gamma), ptr(x), ptr(g), HOST, C.byref(it), C.byref(flags))
+        info = {"iterations": int(it.value), "converged": bool(flags.value & SBL_CONVERGED)}
+        return (x[:self.N], info, g[:self.N]) if return_gamma else (x[:self.N], info)
+
+    def sbl_device(self, b, sigma2, x, gamma_in=None, gamma_out=None, maxiter=None, min_change=1e-6):
+        """torch CUDA tensors: b (M,) float32 / float64; x (N,) float64 receives the dense result; gamma_in (None: ones) and gamma_out
+        (None: not wanted; may be gamma_in) are (N,) float64.  Returns info; the work is done when the call returns."""
+        import torch
+        if not (b.is_cuda and b.is_contiguous() and b.shape == (self.M,) and b.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "b must be a contiguous CUDA vector of length size(A, 1), float32 or float64")
+        for v in (x, gamma_in, gamma_out):
+            if v is not None and not (v.is_cuda and v.is_contiguous() and v.shape == (self.N,) and v.dtype == torch.float64):
+                raise CsmpError(EDIM, "x and gamma must be contiguous CUDA float64 vectors of length size(A, 2)")
+        it, flags = i64(0), C.c_int(0)
+        self.call("csmp_sbl", vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64, C.c_double(sigma2),
+                  i64(128 * self.N if maxiter is None else int(maxiter)), C.c_double(min_change),
+                  vp(gamma_in.data_ptr() if gamma_in is not None else 0), vp(x.data_ptr()),
+                  vp(gamma_out.data_ptr() if gamma_out is not None else 0), DEVICE, C.byref(it), C.byref(flags))
+        return {"iterations": int(it.value), "converged": bool(flags.value & SBL_CONVERGED)}
+
+    def sbl_rowgram(self, gamma, device=False):
+        """csmp_sbl_rowgram (csmp_internal.h): A diag(gamma) Aᵀ as the weighted k_rowgram forms it, Float64 (M, M) -- from and to numpy
+        arrays, or (device=True) torch CUDA tensors"""
+        if device:
+            import torch
+            out = torch.empty((self.M, self.M), dtype=torch.float64, device="cuda")
+            self.call("csmp_sbl_rowgram", vp(gamma.data_ptr()), vp(out.data_ptr()), DEVICE)
+            return out
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+        if gamma.shape != (self.N,):
+            raise CsmpError(EDIM, "length(gamma) has to be size(A, 2)")
+        out = np.zeros((self.M, self.M), np.float64)
+        self.call("csmp_sbl_rowgram", ptr(gamma), ptr(out), HOST)
+        return out
+
+    def sbl_forms(self, W, t, device=False):
+        """csmp_sbl_forms (csmp_internal.h): (s, q), Float64[N] each, from the upper triangular directions W -- Fortran-ordered (ldw, M)
+        with ldw a multiple of 64 -- and t (M,).  numpy arrays, or (device=True) torch CUDA tensors (W as its transpose: (M, ldw)
+        C-contiguous)."""
+        if device:
+            import torch
+            s = torch.empty(max(self.N, 1), dtype=torch.float64, device="cuda")
+            q = torch.empty(max(self.N, 1), dtype=torch.float64, device="cuda")
+            self.call("csmp_sbl_forms", vp(W.data_ptr()), i64(W.shape[1]), vp(t.data_ptr()), vp(s.data_ptr()), vp(q.data_ptr()), DEVICE)
+            return s[:self.N], q[:self.N]
+        W = np.asfortranarray(W, dtype=np.float64)
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != self.M or t.shape != (self.M,):
+            raise CsmpError(EDIM, "W has to be (ldw, size(A, 1)) and t of length size(A, 1)")
+        s, q = np.zeros(max(self.N, 1), np.float64), np.zeros(max(self.N, 1), np.float64)
+        self.call("csmp_sbl_forms", ptr(W), i64(W.shape[0]), ptr(t), ptr(s), ptr(q), HOST)
+        return s[:self.N], q[:self.N]
+
+    def bench_sbl(self, sigma2, reps=5):
+        """csmp_bench_sbl (csmp_internal.h): average ms of the three stages of one update on the last sbl call's gamma and b"""
+        g, f, n = C.c_double(0), C.c_double(0), C.c_double(0)
+        self.call("csmp_bench_sbl", C.c_double(sigma2), int(reps), C.byref(g), C.byref(f), C.byref(n))
+        return {"gram_ms": g.value, "factor_ms": f.value, "forms_ms": n.value}
 
     # ---- dictionary analysis
     def colnorms(self, device=False):

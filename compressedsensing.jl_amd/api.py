@@ -18,6 +18,7 @@ Same names, argument meaning and error behaviour as the reference (paths relativ
     ista(A, b, λ | w[, x]; maxiter, stepsize) / fista(...) / shrinkage(x, α)   src/basispursuit.jl:144,164-204
     bp(A, b[, w]) = basispursuit / bp_candes(A, b, ε) / bp_ard(A, b, ε)         src/basispursuit.jl:1-74
     bpd(A, b, δ[, w]) = basis_pursuit_denoising / bpd_candes(A, b, δ[, ε]) / bpd_ard(A, b, δ[, ε])   src/basispursuit.jl:76-124
+    sbl(A, b, σ²; maxiter, min_change) / SBL functor with update! (scalar σ²)  src/sbl.jl:1-51
     colnorms(A) / coherence(A) / babel(A, k) / cumbabel(A, k)               src/util.jl:2,96-115
 
 `A` is either a numpy matrix (uploaded to HBM for the duration of the call) or a `Dictionary`
@@ -435,6 +436,40 @@ def bpd_ard(A, b, delta, eps=None, *, maxiter=8, min_decrease=1e-4, iter=8, rho=
         raise ValueError(f"iter = {iter} has to be at least 1")
     return _bpd_reweighted(A, b, delta, "ard", delta ** 2 if eps is None else eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every,
                            return_weights, int(iter))
+
+
+# ------------------------------------------------------------------------------------ sparse Bayesian learning
+def _sbl_knobs(A, b, sigma2, maxiter, min_change):
+    M, N, _ = _meta(A)
+    if np.ndim(sigma2) != 0:
+        raise NotImplementedError("sbl: a noise covariance matrix Σ is not served: scalar σ² only")
+    if not (sigma2 > 0 and np.isfinite(sigma2)):
+        raise ValueError(f"σ² = {sigma2} has to be positive and finite")
+    if not min_change >= 0:
+        raise ValueError(f"min_change = {min_change} has to be non-negative")
+    if maxiter is not None and (not _is_int(maxiter) or maxiter < 1):
+        raise ValueError(f"maxiter = {maxiter} has to be at least 1")
+    if np.shape(b) != (M,):
+        raise ValueError(f"DimensionMismatch: size(A, 1) = {M} != {np.shape(b)} = size(b)")
+    return M, N
+
+
+def sbl(A, b, sigma2, *, maxiter=None, min_change=1e-6, return_info=False):
+    """sbl(A, b, σ²; maxiter = 128 size(A, 2), min_change = 1e-6) (src/sbl.jl:37-51): sparse Bayesian learning for a scalar noise variance.
+    From γ = 1, update!(::SBL) (:26-35) until ‖γ_old − γ‖ < min_change or maxiter updates are done; returns the DENSE x of the last update,
+    Float64[N], as the reference does (its entries off the support are tiny, not zero).  Every update runs in the Woodbury form on the
+    M × M matrix σ² I + A Γ Aᵀ (include/csmp.h, csmp_sbl) -- the reference's N × N factorisation is never formed -- so more rows than
+    columns are served.  return_info=True: (x, info) with info = {iterations, converged, gamma}.  Reaching maxiter is no error
+    (converged is False).  A noise covariance matrix raises NotImplementedError; fsbl and rmps are not served."""
+    M, N = _sbl_knobs(A, b, sigma2, maxiter, min_change)
+    D, tmp = _dict(A)
+    try:
+        x, info, gamma = D.ctx.sbl(b, float(sigma2), maxiter, float(min_change), return_gamma=True)
+        info["gamma"] = gamma
+        return (x, info) if return_info else x
+    finally:
+        if tmp:
+            D.close()
 
 
 # ------------------------------------------------------------------------------------ dictionary analysis
@@ -863,6 +898,42 @@ class MP(_DevicePursuit):
             return out.copy()
         x.nzind, x.nzval = out.nzind.copy(), out.nzval.copy()
         return x
+
+
+class SBL(_Update):
+    """SBL(A, b, σ²) = SparseBayesianLearning (src/sbl.jl:4-19) for a scalar noise variance; update!(S, x): :26-35, one csmp_sbl update.
+    The prior variances stay on the device between the calls: `gamma` is a torch CUDA Float64 tensor, ones at the start (Γ = I).  n calls
+    give the bits of sbl(A, b, σ², maxiter=n)."""
+
+    def __init__(self, A, b, sigma2):
+        _sbl_knobs(A, b, sigma2, None, 0.0)
+        import torch
+        self.D, self._tmp = _dict(A)
+        self.A, self.b, self.sigma2 = A, np.asarray(b), float(sigma2)
+        N = self.D.shape[1]
+        self.ctx = self.D.ctx.clone()  # a context of its own that borrows the resident dictionary, as the pursuit functors
+        self._bd = torch.from_numpy(self.ctx._b(b)).cuda()
+        self.gamma = torch.ones(N, dtype=torch.float64, device="cuda")
+        self._xd = torch.zeros(N, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()  # (the library works on a stream of its own)
+        self.iterations = 0
+
+    def update_(self, x=None):
+        self.ctx.sbl_device(self._bd, self.sigma2, self._xd, self.gamma, self.gamma, maxiter=1, min_change=0.0)
+        self.iterations += 1
+        out = self._xd.cpu().numpy()
+        if x is None:
+            return out
+        x[:] = out
+        return x
+
+    def close(self):
+        self.ctx.close()
+        if self._tmp:
+            self.D.close()
+
+
+SparseBayesianLearning = SBL
 
 
 class _TwoStage(_Update):

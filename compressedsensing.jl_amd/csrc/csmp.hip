@@ -21,6 +21,7 @@
 #include "csmp_reweight.hpp"
 #include "csmp_bp.hpp"
 #include "csmp_bpd.hpp"
+#include "csmp_sbl.hpp"
 
 #include <algorithm>
 #include <iterator>
@@ -60,5 +61,6 @@ using namespace csmp;
 #include "host/reweight.hpp"
 #include "host/bp.hpp"
 #include "host/bpd.hpp"
+#include "host/sbl.hpp"
 #include "host/measure.hpp"
 #include "host/rccl.hpp"

@@ -34,9 +34,11 @@ __host__ __device__ constexpr size_t rowgram_lds_bytes() { return (size_t)2 * 2 
 // operands.  Double-buffered: the next stage's loads are in flight under the current stage's 64 MFMAs per wave.  Rows beyond M and
 // columns beyond the split's end are loaded from clamped addresses and staged as zeros; stores are masked.  VEC: the columns start
 // on 16-byte boundaries -- 16-byte loads wherever the vector lies inside the column.  A diagonal tile stages one block.
-template <typename TA, bool VEC>
+// WT (csmp_sbl.hpp): the sum is weighted,  sum gam[c] a_c a_c' -- the second operand is scaled by gam[c] as it is staged (one rounding
+// per entry), so a diagonal tile stages both blocks too.  WT = false reads no gam and does what it did before the flag existed.
+template <typename TA, bool VEC, bool WT = false>
 __global__ __launch_bounds__(256) void k_rowgram(const TA* __restrict__ A, int64_t ld, int M, int64_t N, int64_t cols_per_split,
-                                                 double* __restrict__ Gpart) {
+                                                 double* __restrict__ Gpart, const double* __restrict__ gam = nullptr) {
     typedef double d4 __attribute__((ext_vector_type(4)));
     typedef TA tav __attribute__((ext_vector_type(16 / sizeof(TA))));
     constexpr int PERV = 16 / (int)sizeof(TA), GPC = kRgTile / PERV, NQ = kRgKC * GPC / 256, S = kRgStride;
@@ -49,8 +51,10 @@ __global__ __launch_bounds__(256) void k_rowgram(const TA* __restrict__ A, int64
     const bool diag = I == J;
     const int64_t c0 = (int64_t)blockIdx.y * cols_per_split, c1 = c0 + cols_per_split < N ? c0 + cols_per_split : N;
     const int nst = (int)((c1 - c0 + kRgKC - 1) / kRgKC);
-    const int nop = diag ? 1 : 2;
+    const bool one = diag && !WT;  // both operands are the same staged block
+    const int nop = one ? 1 : 2;
     TA raw[2][NQ][PERV];
+    double gw[NQ];
     d4 acc[4][4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -67,6 +71,7 @@ __global__ __launch_bounds__(256) void k_rowgram(const TA* __restrict__ A, int64
                 const int g = tid + 256 * q, cl = g / GPC, r = rb + (g % GPC) * PERV;
                 const int64_t c = c0 + (int64_t)st * kRgKC + cl;
                 const TA* col = A + (c < c1 ? c : c1 - 1) * ld;
+                if (WT && h == 1) gw[q] = gam[c < c1 ? c : c1 - 1];
                 if (VEC && r + PERV <= M) {
                     const tav x = *reinterpret_cast<const tav*>(col + r);
 #pragma unroll
@@ -93,6 +98,10 @@ __global__ __launch_bounds__(256) void k_rowgram(const TA* __restrict__ A, int64
                     f64x2 v;
                     v.x = (colok && rb + rl + e < M) ? (double)raw[h][q][e] : 0.0;
                     v.y = (colok && rb + rl + e + 1 < M) ? (double)raw[h][q][e + 1] : 0.0;
+                    if (WT && h == 1) {
+                        v.x *= gw[q];
+                        v.y *= gw[q];
+                    }
                     *reinterpret_cast<f64x2*>(dst + cl * S + rl + e) = v;
                 }
             }
@@ -100,7 +109,7 @@ __global__ __launch_bounds__(256) void k_rowgram(const TA* __restrict__ A, int64
     };
     auto compute = [&](int buf) {
         const double* pa = rglds + (size_t)(buf * 2) * kRgKC * S + wi * 64 + fr;
-        const double* pb = rglds + (size_t)(buf * 2 + (diag ? 0 : 1)) * kRgKC * S + wj * 64 + fr;
+        const double* pb = rglds + (size_t)(buf * 2 + (one ? 0 : 1)) * kRgKC * S + wj * 64 + fr;
 #pragma unroll
         for (int kk = 0; kk < kRgKC / 4; ++kk) {
             double a[4], b[4];

@@ -24,7 +24,7 @@ static hipError_t rowgram_t(csmp_ctx* ctx, int nsplit, int64_t cps, double* Gpar
     if (e != hipSuccess) return e;
     const int64_t T = (ctx->M + kRgTile - 1) / kRgTile;
     hipLaunchKernelGGL(kern, dim3((unsigned)(T * (T + 1) / 2), (unsigned)nsplit), dim3(256), rowgram_lds_bytes(), ctx->stream, (const TA*)ctx->dA,
-                       ctx->ld, (int)ctx->M, ctx->N, cps, Gpart);
+                       ctx->ld, (int)ctx->M, ctx->N, cps, Gpart, (const double*)nullptr);
     return hipGetLastError();
 }
 // G = A A' into Gdst (M x M doubles, device).  The partials are a temporary of the call.

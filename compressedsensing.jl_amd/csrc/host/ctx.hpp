@@ -191,6 +191,22 @@ struct BpdBuf {
     bool notpd = false;     // ... and the factorisation met a pivot that is not positive (K is positive definite: a fault, not a verdict on A)
 };
 
+// sparse Bayesian learning (csmp_sbl.hpp, host/sbl.hpp): k_rowgram's partials of A Gamma A' and their sum G (M x M), the augmented
+// matrix [C | I], C = sigma2 I + G, that the blocked Cholesky turns into R beside R^-T (BpBuf's layout; R^-1 = L^-T in its rows from np
+// on), the M-vectors b and t = L^-1 b, the N-vectors gam, s, q and x, the partials and the verdicts, made on first use, sized by the
+// dictionary: all of them, or none.  Apart from BpBuf and BpdBuf: nothing here is kept from one call to the next but the memory.
+struct SblBuf {
+    double *Gpart = nullptr, *G = nullptr, *Gm = nullptr, *pivref = nullptr, *Dfac = nullptr, *vec = nullptr, *gam = nullptr, *s = nullptr,
+           *q = nullptr, *x = nullptr, *part = nullptr;
+    SblInfo* info = nullptr;
+    DevState* st = nullptr;
+    int M = 0, np = 0;  // rows the buffers were made for (0: none)
+    int64_t N = 0;      // ... and atoms
+    int Mp = 0;         // length of each of the two M-vectors b, t in vec
+    int nsplit = 0;     // k_rowgram's column splits (bp_rowgram_split)
+    int64_t cps = 0;
+};
+
 struct csmp_ctx;
 // Subspace Pursuit as a resumable job: see host/gomp_sp.hpp
 struct SpJob {
@@ -263,6 +279,7 @@ struct csmp_ctx {
     int tune_rebuild_direct = 0;  // csmp_tune: the oblivious start's Q'A pass reads its directions from L2 (k_fr_rebuild) instead of the LDS
     int tune_swap_refuse = 0;  // csmp_tune: OMPR's inverse-Gram exchanges fail their guard (tests walk the fallback to the QR path)
     int tune_rowgram_scalar = 0;  // csmp_tune: k_rowgram without 16-byte loads
+    int tune_sbl_scalar = 0;      // csmp_tune: csmp_sbl's weighted k_rowgram and k_sbl_forms without 16-byte loads
     int tune_pass_c = 0;      // csmp_tune: 1 = the grouped OMP scheduler's passes store c, which nothing reads (shared_pass_launch)
     int tune_group_split = 0; // csmp_tune: how the grouped scheduler cuts a batch into wide groups, narrow_last_groups' split (1 = evenly)
     int tune_diag_split = 0;  // csmp_tune: fused kernels run as one launch per part (a kernel trace then shows the parts)
@@ -301,6 +318,7 @@ struct csmp_ctx {
     RwBuf rw;
     BpBuf bp;
     BpdBuf bpd;
+    SblBuf sbl;
     // profiling
     bool prof = false;
     int prof_every = 1;       // time every n-th sweep launch only (an event pair costs a few us of stream time)

@@ -249,6 +249,7 @@ static int dict_forget(csmp_ctx* ctx) {
     rw_free(ctx->rw);
     bp_free(ctx->bp);
     bpd_free(ctx->bpd);
+    sbl_free(ctx->sbl);
     return CSMP_OK;
 }
 

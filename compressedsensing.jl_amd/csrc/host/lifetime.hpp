@@ -112,6 +112,12 @@ static void bpd_free(BpdBuf& t) {
     t = BpdBuf();
 }
 
+static void sbl_free(SblBuf& t) {
+    dfree(t.Gpart); dfree(t.G); dfree(t.Gm); dfree(t.pivref); dfree(t.Dfac); dfree(t.vec); dfree(t.gam); dfree(t.s); dfree(t.q); dfree(t.x);
+    dfree(t.part); dfree(t.info); dfree(t.st);
+    t = SblBuf();
+}
+
 static void dict_release(csmp_ctx* ctx) {
     if (ctx->share && --ctx->share->refs == 0) {
         if (ctx->share->kind == 0) (void)hipFree(ctx->share->p);
@@ -139,6 +145,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     rw_free(ctx->rw);
     bp_free(ctx->bp);
     bpd_free(ctx->bpd);
+    sbl_free(ctx->sbl);
     if (ctx->comm) (void)csmp_comm_free(ctx);
     for (auto& t : ctx->twins) {
         if (t) (void)csmp_destroy(t);

@@ -309,6 +309,41 @@ bpd_ard(A::MatOrDict, b::AbstractVector, δ::Real, ε::Real = δ^2; maxiter::Int
         inner_maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32, return_weights::Bool = false) =
     bpd_reweighted(A, b, δ, CSMP_REWEIGHT_ARD, ε, iter, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights)
 
+# ---------------------------------------------------------------------------------- sparse Bayesian learning
+# src/sbl.jl:1-51: sbl(A, b, σ²) and SBL(A, b, σ²) with update! for a SCALAR noise variance, in the Woodbury form on the M × M matrix
+# σ² I + A Γ Aᵀ (csmp_sbl, include/csmp.h).  A noise covariance matrix Σ is not served, nor are fsbl and rmps.
+const CSMP_SBL_CONVERGED = 1
+function sbl_call(D::Dictionary, b::AbstractVector, σ²::Real, γ::Vector{Float64}, maxiter::Int, min_change::Real)
+    bb, bt = bvec(b)
+    xd = zeros(Float64, size(D, 2))
+    it, flags = Ref{Int64}(0), Ref{Cint}(0)
+    GC.@preserve bb γ xd check(D, ccall((:csmp_sbl, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Int64, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ref{Int64}, Ref{Cint}),
+        D.ctx, bb, bt, σ², maxiter, min_change, γ, xd, γ, CSMP_HOST, it, flags))
+    return xd, (iterations = Int(it[]), converged = flags[] & CSMP_SBL_CONVERGED != 0, gamma = γ)
+end
+function sbl(A::MatOrDict, b::AbstractVector, σ²::Real; maxiter::Int = 128size(A, 2), min_change::Real = 1e-6, return_info::Bool = false)
+    xd, info = sbl_call(dict(A), b, σ², ones(Float64, size(A, 2)), maxiter, min_change)
+    return return_info ? (xd, info) : xd
+end
+sbl(A::MatOrDict, b::AbstractVector, Σ::AbstractMatrix; kwargs...) = error("sbl: a noise covariance matrix Σ is not served: scalar σ² only")
+# SBL(A, b, σ²): the prior variances Γ.diag live in `gamma`, ones at the start; update!(S, x) is one csmp_sbl update (:26-35)
+struct SparseBayesianLearning
+    D::Dictionary
+    b::Vector{Float64}
+    σ²::Float64
+    gamma::Vector{Float64}
+end
+const SBL = SparseBayesianLearning
+SBL(A::MatOrDict, b::AbstractVector, σ²::Real) = SparseBayesianLearning(dict(A), convert(Vector{Float64}, b), Float64(σ²), ones(Float64, size(A, 2)))
+SBL(A::MatOrDict, b::AbstractVector, Σ::AbstractMatrix) = error("SBL: a noise covariance matrix Σ is not served: scalar σ² only")
+function update!(S::SparseBayesianLearning, x::AbstractVector = zeros(length(S.gamma)))
+    xd, _ = sbl_call(S.D, S.b, S.σ², S.gamma, 1, 0.0)
+    x .= xd
+    return x
+end
+(S::SparseBayesianLearning)(x::AbstractVector = zeros(length(S.gamma))) = update!(S, x)
+
 # ---------------------------------------------------------------------------------- dictionary analysis
 # src/util.jl:2,96-115: colnorms, coherence, babel, cumbabel.  The inner products are raw, as in the reference (which assumes unit-norm
 # columns); normalize = true divides each by ‖a_i‖ ‖a_j‖.  cumbabel_pair also returns the columns (i, j), i < j, 1-based, that attain

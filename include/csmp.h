@@ -509,6 +509,37 @@ int csmp_bpd_reweighted(csmp_ctx *ctx, const void *b, int b_dtype, double delta,
                         int64_t outer_maxiter, double min_decrease, double rho, int64_t maxiter, double tol, int64_t check_every,
                         double *x, int x_loc, double *w_out, int64_t *outer_done, double *resnorm);
 
+/* ------------------------------------------------------------------ sparse Bayesian learning
+ * sbl(A, b, sigma2) and update!(::SBL): src/sbl.jl:1-51, for a scalar noise variance sigma2 (a matrix Sigma is not served; fsbl and
+ * rmps, :57-470, are not served either).  The reference factorises the N x N matrix A'A / sigma2 + Gamma^-1 in every update; this is
+ * the same update in the Woodbury form, on the M x M matrix
+ *     C = sigma2 I + A Gamma A' = L L',   Gamma = diag(gamma)
+ * -- positive definite for EVERY dictionary, so size(A,1) > size(A,2) is served.  For every atom j
+ *     s_j = |L^-1 a_j|^2;   q_j = (L^-1 a_j)' (L^-1 b);   x_j = gamma_j q_j;   gamma_j+ = gamma_j q_j^2 / s_j + 1e-14
+ * (B^-1 = Gamma - Gamma A' C^-1 A Gamma, so 1 - diag(B^-1)_j / gamma_j = gamma_j s_j and B^-1 A' b / sigma2 = Gamma A' C^-1 b: :26-35
+ * exactly, without the cancellation in 1 - diag / gamma).  A zero column has s_j = 0: x_j = 0 and gamma_j+ = 1e-14.  One update is two
+ * M x M x N products on the Float64 matrix cores (A Gamma A', and the projections of every atom on the columns of L^-T, of which the
+ * triangle's zero half is skipped), one M x M Cholesky factorisation and ONE host read.
+ * The loop is sbl's (:38-51): from gamma = gamma_in (NULL: ones), after every update stop when ||gamma_old - gamma||_2 < min_change (the
+ * reference's default: 1e-6), at the latest after maxiter updates (the reference's default: 128 size(A,2)); reaching maxiter is not an
+ * error.  maxiter = 1 is update!: gamma_out of one call is the gamma_in of the next.
+ * x: the DENSE result of the last update, Float64[size(A,2)]; gamma_in (may be NULL), gamma_out (may be NULL; may be gamma_in):
+ * Float64[size(A,2)].  loc says where b, x, gamma_in and gamma_out live: CSMP_HOST, or CSMP_DEVICE (the call still returns with the
+ * work done).  iterations (updates done), flags: may be NULL.  flags: CSMP_SBL_CONVERGED -- the last update moved gamma by less than
+ * min_change.
+ * Memory, kept by the context until csmp_set_dictionary, apart from csmp_bp's and csmp_bpd's factors (no call here reads or invalidates
+ * them): the augmented matrix of the factorisation, (2 M)^2 doubles with M rounded up to 64, A Gamma A' and its column-split partials
+ * (M x M doubles each; one split where the upper 128 x 128 tiles alone fill the device) -- 512 MiB + 128 MiB + 128 MiB at 4096 x 65536
+ * -- and four vectors of size(A,2) doubles.
+ * CSMP_EINVAL: null pointers, a b_dtype / loc that is neither, sigma2 not positive and finite, min_change negative or NaN, maxiter < 1,
+ * an entry of gamma_in that is not positive and finite, "sbl: sigma2 I + A Gamma A' is not positive definite to working precision" (a
+ * pivot of the factorisation below 4 M eps of its diagonal entry: csmp_bp's rule), and a gamma that comes out negative or not finite.
+ * CSMP_ERANGE: more than 2^19 rows.  CSMP_ESTATE: no dictionary -- and a host-streamed dictionary (CSMP_HOST_STREAMED), as csmp_ista.
+ * CSMP_ENOMEM: a buffer could not be allocated; none of them is left behind, and the next call starts afresh. */
+#define CSMP_SBL_CONVERGED 1
+int csmp_sbl(csmp_ctx *ctx, const void *b, int b_dtype, double sigma2, int64_t maxiter, double min_change,
+             const double *gamma_in, double *x, double *gamma_out, int loc, int64_t *iterations, int *flags);
+
 /* ------------------------------------------------------------------ dictionary analysis
  * colnorms(A): src/util.jl:2.  norms[j] = ||a_j||_2 of every column of the resident dictionary, N doubles, to host memory
  * (out_loc = CSMP_HOST) or device memory (CSMP_DEVICE; the call still returns with the work done).  Float64 on the exactly

@@ -41,6 +41,20 @@ int csmp_bench_ard_forms(csmp_ctx *ctx, int variant, int reps, double eps, doubl
 /* G = A A' of the resident dictionary by k_rowgram and its reduction alone (csmp_bp forms it once per dictionary and keeps it): M x M
  * doubles, column-major and exactly symmetric, to host (loc = CSMP_HOST) or device memory (CSMP_DEVICE).  Nothing of the context changes. */
 int csmp_bp_rowgram(csmp_ctx *ctx, double *G_out, int loc);
+/* C0 = A diag(gamma) A' of the resident dictionary by the weighted k_rowgram and its reduction alone (the first stage of a csmp_sbl
+ * update): M x M doubles, column-major and exactly symmetric.  gamma: size(A,2) doubles.  loc says where gamma and C_out live
+ * (CSMP_HOST / CSMP_DEVICE).  The column splits are csmp_bp_rowgram's.  Nothing of the context changes. */
+int csmp_sbl_rowgram(csmp_ctx *ctx, const double *gamma, double *C_out, int loc);
+/* k_sbl_forms alone (the N-pass of a csmp_sbl update) on directions of the caller's:  s_j = sum_d (w_d' a_j)^2,  q_j = sum_d (w_d' a_j) t_d
+ * for every atom j, w_d = column d of W, d = 0 .. M - 1.  W: column-major with leading dimension ldw, a multiple of 64 that is at least
+ * M, UPPER TRIANGULAR: of column d the kernel uses the rows 0 .. d and nothing else -- with D = d / 128, the 64-row blocks from row
+ * 128 (D + 1) on are never read, and inside the blocks that are read an entry below the diagonal counts as zero whatever it holds.
+ * t: M doubles; s, q: size(A,2) doubles.  loc says where all four live; a device W starts on a 16-byte boundary.  CSMP_EDIM: ldw. */
+int csmp_sbl_forms(csmp_ctx *ctx, const double *W, int64_t ldw, const double *t, double *s, double *q, int loc);
+/* the three stages of one csmp_sbl update on the gamma and b the LAST csmp_sbl call of this context left behind, each bracketed by HIP
+ * events: the weighted Gram matrix and its reduction; the assembly, the factorisation, L^-T and t = L^-1 b; k_sbl_forms.  The averages
+ * (ms) of `reps` runs after one warm-up run; gamma is not updated.  Any pointer may be NULL.  CSMP_ESTATE: no such call has been made. */
+int csmp_bench_sbl(csmp_ctx *ctx, double sigma2, int reps, double *gram_ms, double *factor_ms, double *forms_ms);
 /* what configure_sweep chose for the resident dictionary: loads per unit of k_sweep_gen (16 / 8 / 4); phases the residual is
  * staged in (1: one LDS image); workgroups of a stand-alone sweep and of the sweep inside the tick kernel; dynamic LDS bytes;
  * dynamic = 1: the columns are handed out at run time (k_sweep_dyn and the DYN tick), 0: split statically; columns_per_unit: 2 or 4
@@ -62,6 +76,7 @@ int csmp_sweep_group_wide(const csmp_ctx *ctx, int *group_wide);
 #define CSMP_TUNE_GROUP_MAX 20    /* largest group of the grouped scheduler (CSMP_TUNE_PIPELINES 3); 0 = as many residual images as the LDS holds, at most 4 */
 #define CSMP_TUNE_GROUP_WIDE 21   /* 1: no wide groups (every pass serves at most group_max signals); 2: wide groups, the three of a round on ONE pipeline (a measurement: slower); default 0: batches of more signals than that run groups of up to 2 * group_max wherever the grouped scheduler has group_max = 4 images per workgroup on a Float32 dictionary and CSMP_TUNE_GROUP_MAX is 0.  CSMP_TUNE_TICK_GRID overrides the wide pass's grid too, rounded down to a multiple of 16 */
 #define CSMP_TUNE_ROWGRAM_SCALAR 22 /* 1: k_rowgram (csmp_bp, csmp_bp_rowgram) loads the dictionary with scalar loads, as for columns that start on no 16-byte boundary (the library's own copy always does: tests reach that instantiation here); the same bits */
+#define CSMP_TUNE_SBL_SCALAR 25   /* 1: csmp_sbl's kernels that read the dictionary (the weighted k_rowgram, k_sbl_forms; csmp_sbl_rowgram and csmp_sbl_forms too) load it with scalar loads, as for columns that start on no 16-byte boundary; the same bits */
 #define CSMP_TUNE_PASS_C 23       /* 1: the shared passes of csmp_omp_batch's grouped scheduler store every member's c = A'r, which nothing reads there; default 0: they store none (csmp_mp_batch's passes always do).  The same results */
 #define CSMP_TUNE_GROUP_SPLIT 24  /* how the grouped scheduler cuts a batch into WIDE groups (host/batch_plan.hpp: narrow_last_groups).  Default 0: ceil(nsig / group_wide) groups, the last one of group_max signals -- a narrow pass -- where that takes no pass more (18 signals: 8 + 6 + 4); 1: as even as possible (6 + 6 + 6); 2, 3: measurements (7 + 7 + 4, 8 + 8 + 2).  The same results */
 #define CSMP_TUNE_TICK_ORDER 10   /* 1: the tick kernel's sweep workgroups are dispatched ahead of its append stages' */
