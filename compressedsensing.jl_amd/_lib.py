@@ -94,6 +94,9 @@ SIGNATURES = {
     "csmp_bpd_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, i64, i64, C.c_double, C.c_double, i64, C.c_double, i64, vp, C.c_int,
                                       vp, C.POINTER(i64), C.POINTER(C.c_double)]),
     "csmp_sbl": (C.c_int, [vp, vp, C.c_int, C.c_double, i64, C.c_double, vp, vp, vp, C.c_int, C.POINTER(i64), C.POINTER(C.c_int)]),
+    "csmp_fsbl": (C.c_int, [vp, vp, C.c_int, C.c_double, i64, C.c_double, vp, vp, vp, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(C.c_int)]),
+    "csmp_rmps": (C.c_int, [vp, vp, C.c_int, C.c_double, i64, i64, i64, C.c_double, vp, vp, vp, C.c_int, vp, i64, C.POINTER(i64),
+                            C.POINTER(C.c_int)]),
     "csmp_colnorms": (C.c_int, [vp, vp, C.c_int]),
     "csmp_cumbabel": (C.c_int, [vp, i64, C.c_int, vp, vp]),
     "csmp_sweep": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -111,6 +114,9 @@ INTERNAL_SIGNATURES = {
     "csmp_sbl_rowgram": (C.c_int, [vp, vp, vp, C.c_int]),
     "csmp_sbl_forms": (C.c_int, [vp, vp, i64, vp, vp, vp, C.c_int]),
     "csmp_bench_sbl": (C.c_int, [vp, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "csmp_fsbl_score": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "csmp_fsbl_sqc": (C.c_int, [vp, vp, vp, vp, i64, C.c_double]),
+    "csmp_bench_fsbl": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "csmp_profile_overhead": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
     "csmp_live_resources": (C.c_int, [C.POINTER(i64)] * 6),
     "csmp_profile_window": (C.c_int, [vp, C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
@@ -121,7 +127,7 @@ INTERNAL_SIGNATURES = {
     "csmp_batch_layout": (C.c_int, [vp, C.POINTER(i64), C.POINTER(C.c_int)]),
     "csmp_batch_screen_kernel": (C.c_char_p, [vp]),
 }
-TUNE = {"sweep_grid": 2, "sweep_unit": 3, "tick_grid": 4, "batch_budget_mib": 5, "diag_split": 6, "swap_refuse": 7, "rebuild_direct": 8, "sweep_dyn": 9, "tick_order": 10, "claim_pools": 11, "pipelines": 12, "pair_lds_kib": 13, "pair_split": 14, "sweep_lds_kib": 15, "sweep_short": 16, "phase_rows": 17, "fail_alloc": 18, "screen_static": 19, "group_max": 20, "group_wide": 21, "rowgram_scalar": 22, "pass_c": 23, "group_split": 24, "sbl_scalar": 25}  # CSMP_TUNE_* (include/csmp_internal.h)
+TUNE = {"sweep_grid": 2, "sweep_unit": 3, "tick_grid": 4, "batch_budget_mib": 5, "diag_split": 6, "swap_refuse": 7, "rebuild_direct": 8, "sweep_dyn": 9, "tick_order": 10, "claim_pools": 11, "pipelines": 12, "pair_lds_kib": 13, "pair_split": 14, "sweep_lds_kib": 15, "sweep_short": 16, "phase_rows": 17, "fail_alloc": 18, "screen_static": 19, "group_max": 20, "group_wide": 21, "rowgram_scalar": 22, "pass_c": 23, "group_split": 24, "sbl_scalar": 25, "fsbl_scalar": 26}  # CSMP_TUNE_* (include/csmp_internal.h)
 
 COMM_ID_BYTES = 128  # CSMP_COMM_ID_BYTES
 BABEL_KMAX = 1024  # CSMP_BABEL_KMAX
@@ -131,6 +137,8 @@ BP_CONVERGED, BP_FACTORED = 1, 2  # CSMP_BP_*
 BPD_CONVERGED, BPD_FACTORED = 1, 2  # CSMP_BPD_*
 BPD_RHO = 100.0  # the bindings' default penalty of bpd
 SBL_CONVERGED = 1  # CSMP_SBL_*
+FSBL_CONVERGED = RMPS_CONVERGED = 1  # CSMP_FSBL_*, CSMP_RMPS_*
+FSBL_MODES = {"all": 1, "add": 2, "rmp_delete": 3, "update": 4}  # csmp_fsbl_score's modes
 
 
 def live_resources():
@@ -955,6 +963,109 @@ class Context:
         g, f, n = C.c_double(0), C.c_double(0), C.c_double(0)
         self.call("csmp_bench_sbl", C.c_double(sigma2), int(reps), C.byref(g), C.byref(f), C.byref(n))
         return {"gram_ms": g.value, "factor_ms": f.value, "forms_ms": n.value}
+
+    # ---- greedy sparse Bayesian learning
+    def _greedy(self, name, b, sigma2, caps, min_increase, alpha_in, x, alpha_out, loc, history_cap):
+        """csmp_fsbl / csmp_rmps: caps are the call's iteration caps in the prototype's order; returns info"""
+        cap = max(int(history_cap), 0)
+        hist = np.zeros((max(cap, 1), 2), np.int64)
+        it, flags = i64(0), C.c_int(0)
+        self.call(name, b[0], b[1], C.c_double(sigma2), *[i64(int(c)) for c in caps], C.c_double(min_increase), alpha_in, x, alpha_out, loc,
+                  ptr(hist), i64(cap), C.byref(it), C.byref(flags))
+        return {"iterations": int(it.value), "converged": bool(flags.value & FSBL_CONVERGED)}, hist
+
+    def _greedy_host(self, name, b, sigma2, caps, min_increase, alpha, history_cap):
+        b = self._b(b)
+        if alpha is not None:
+            alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+            if alpha.shape != (self.N,):
+                raise CsmpError(EDIM, "length(alpha) has to be size(A, 2)")
+        x = np.zeros(max(self.N, 1), np.float64)
+        a = np.zeros(max(self.N, 1), np.float64)
+        info, hist = self._greedy(name, (ptr(b), dtype_code(b.dtype)), sigma2, caps, min_increase, ptr(alpha), ptr(x), ptr(a), HOST, history_cap)
+        info["alpha"] = a[:self.N]
+        return x[:self.N], info, hist
+
+    def fsbl(self, b, sigma2, maxiter=None, min_increase=1e-6, alpha=None, history_cap=None):
+        """csmp_fsbl on a host signal: (x, Float64[N], exactly 0 off the active set; info = iterations (passes), converged, alpha, history:
+        the (action, index) pairs of the applied steps, 1 add, 2 delete, 3 re-estimate).  maxiter=None: 2 N, the reference's default.
+        alpha: the N prior precisions to start from (+inf: inactive; None: all inactive).  history_cap=None: room for every pass.  The
+        first call on a dictionary allocates M² doubles and five N-vectors of device memory, kept until the dictionary changes."""
+        maxiter = 2 * self.N if maxiter is None else int(maxiter)
+        cap = max(maxiter, 0) if history_cap is None else int(history_cap)
+        x, info, hist = self._greedy_host("csmp_fsbl", b, sigma2, (maxiter,), min_increase, alpha, cap)
+        return x, self._history(info, hist, cap, None)
+
+    def rmps(self, b, sigma2, maxiter=None, maxiter_acquisition=None, maxiter_deletion=None, min_increase=1e-6, alpha=None, history_cap=None):
+        """csmp_rmps on a host signal: as fsbl; the three caps default to M, the reference's; iterations counts the applied steps.
+        history_cap=None: the whole history (a run longer than 4 N steps is run again with the room it needs)."""
+        caps = tuple(self.M if c is None else int(c) for c in (maxiter, maxiter_acquisition, maxiter_deletion))
+        cap = 4 * self.N if history_cap is None else int(history_cap)
+        x, info, hist = self._greedy_host("csmp_rmps", b, sigma2, caps, min_increase, alpha, cap)
+        if history_cap is None and info["iterations"] > cap:
+            cap = info["iterations"]
+            x, info, hist = self._greedy_host("csmp_rmps", b, sigma2, caps, min_increase, alpha, cap)
+        return x, self._history(info, hist, cap, info["iterations"])
+
+    @staticmethod
+    def _history(info, hist, cap, applied):
+        """the recorded pairs: the applied steps where known (rmps), else the rows an action was written to (fsbl: at most one a pass)"""
+        n = min(cap, applied) if applied is not None else int(np.count_nonzero(hist[:max(cap, 0), 0]))
+        info["history"] = [(int(a), int(i)) for a, i in hist[:n]]
+        return info
+
+    def fsbl_device(self, b, sigma2, x, alpha_in=None, alpha_out=None, maxiter=None, min_increase=1e-6, history_cap=0):
+        """torch CUDA tensors: b (M,) float32 / float64; x (N,) float64 receives the result; alpha_in (None: all +inf) and alpha_out
+        (None: not wanted; may be alpha_in) are (N,) float64.  Returns info; the work is done when the call returns."""
+        args = self._greedy_device(b, x, alpha_in, alpha_out)
+        maxiter = 2 * self.N if maxiter is None else int(maxiter)
+        info, hist = self._greedy("csmp_fsbl", args[0], sigma2, (maxiter,), min_increase, *args[1:], DEVICE, history_cap)
+        return self._history(info, hist, int(history_cap), None)
+
+    def rmps_device(self, b, sigma2, x, alpha_in=None, alpha_out=None, maxiter=None, maxiter_acquisition=None, maxiter_deletion=None,
+                    min_increase=1e-6, history_cap=0):
+        """as fsbl_device, for csmp_rmps"""
+        args = self._greedy_device(b, x, alpha_in, alpha_out)
+        caps = tuple(self.M if c is None else int(c) for c in (maxiter, maxiter_acquisition, maxiter_deletion))
+        info, hist = self._greedy("csmp_rmps", args[0], sigma2, caps, min_increase, *args[1:], DEVICE, history_cap)
+        return self._history(info, hist, int(history_cap), info["iterations"])
+
+    def _greedy_device(self, b, x, alpha_in, alpha_out):
+        import torch
+        if not (b.is_cuda and b.is_contiguous() and b.shape == (self.M,) and b.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "b must be a contiguous CUDA float32 / float64 vector of length size(A, 1)")
+        for v in (x, alpha_in, alpha_out):
+            if v is not None and not (v.is_cuda and v.is_contiguous() and v.shape == (self.N,) and v.dtype == torch.float64):
+                raise CsmpError(EDIM, "x and alpha must be contiguous CUDA float64 vectors of length size(A, 2)")
+        return ((vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64), vp(alpha_in.data_ptr() if alpha_in is not None else 0),
+                vp(x.data_ptr()), vp(alpha_out.data_ptr() if alpha_out is not None else 0))
+
+    def fsbl_score(self, alpha, S, Q, mode):
+        """csmp_fsbl_score (csmp_internal.h): (values Float64[N], pick, value, action) of one N-pass on a state of the caller's; mode: a key
+        of FSBL_MODES"""
+        arrs = [np.ascontiguousarray(v, dtype=np.float64) for v in (alpha, S, Q)]
+        if any(v.shape != (self.N,) for v in arrs):
+            raise CsmpError(EDIM, "alpha, S and Q have to be of length size(A, 2)")
+        vals = np.zeros(max(self.N, 1), np.float64)
+        pick, value, action = i64(0), C.c_double(0), C.c_int(0)
+        self.call("csmp_fsbl_score", ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), int(FSBL_MODES[mode]), ptr(vals), C.byref(pick), C.byref(value),
+                  C.byref(action))
+        return vals[:self.N], int(pick.value), value.value, int(action.value)
+
+    def fsbl_sqc(self, Cinv, S, Q, i, gamma):
+        """csmp_fsbl_sqc (csmp_internal.h): (C⁻¹, S, Q) after the rank-one step sqc(i, gamma) on a state of the caller's"""
+        Cinv = np.array(Cinv, dtype=np.float64, order="F")
+        S, Q = np.array(S, dtype=np.float64), np.array(Q, dtype=np.float64)
+        if Cinv.shape != (self.M, self.M) or S.shape != (self.N,) or Q.shape != (self.N,):
+            raise CsmpError(EDIM, "Cinv has to be (size(A, 1), size(A, 1)), S and Q of length size(A, 2)")
+        self.call("csmp_fsbl_sqc", ptr(Cinv), ptr(S), ptr(Q), i64(int(i)), C.c_double(gamma))
+        return Cinv, S, Q
+
+    def bench_fsbl(self, reps=5):
+        """csmp_bench_fsbl (csmp_internal.h): average ms of the four parts of one greedy step on the state the last fsbl / rmps call left"""
+        v = [C.c_double(0) for _ in range(4)]
+        self.call("csmp_bench_fsbl", int(reps), *[C.byref(u) for u in v])
+        return dict(zip(("score_ms", "colgemv_ms", "rank1_ms", "sweep_ms"), (u.value for u in v)))
 
     # ---- dictionary analysis
     def colnorms(self, device=False):

@@ -19,6 +19,7 @@ Same names, argument meaning and error behaviour as the reference (paths relativ
     bp(A, b[, w]) = basispursuit / bp_candes(A, b, ε) / bp_ard(A, b, ε)         src/basispursuit.jl:1-74
     bpd(A, b, δ[, w]) = basis_pursuit_denoising / bpd_candes(A, b, δ[, ε]) / bpd_ard(A, b, δ[, ε])   src/basispursuit.jl:76-124
     sbl(A, b, σ²; maxiter, min_change) / SBL functor with update! (scalar σ²)  src/sbl.jl:1-51
+    fsbl(A, b, σ²; maxiter, min_increase) / rmps(A, b, σ²; ...) / FSBL functor with update! (scalar σ²)  src/sbl.jl:57-437
     colnorms(A) / coherence(A) / babel(A, k) / cumbabel(A, k)               src/util.jl:2,96-115
 
 `A` is either a numpy matrix (uploaded to HBM for the duration of the call) or a `Dictionary`
@@ -460,12 +461,70 @@ def sbl(A, b, sigma2, *, maxiter=None, min_change=1e-6, return_info=False):
     Float64[N], as the reference does (its entries off the support are tiny, not zero).  Every update runs in the Woodbury form on the
     M × M matrix σ² I + A Γ Aᵀ (include/csmp.h, csmp_sbl) -- the reference's N × N factorisation is never formed -- so more rows than
     columns are served.  return_info=True: (x, info) with info = {iterations, converged, gamma}.  Reaching maxiter is no error
-    (converged is False).  A noise covariance matrix raises NotImplementedError; fsbl and rmps are not served."""
+    (converged is False).  A noise covariance matrix raises NotImplementedError; fsbl and rmps are the greedy forms, below."""
     M, N = _sbl_knobs(A, b, sigma2, maxiter, min_change)
     D, tmp = _dict(A)
     try:
         x, info, gamma = D.ctx.sbl(b, float(sigma2), maxiter, float(min_change), return_gamma=True)
         info["gamma"] = gamma
+        return (x, info) if return_info else x
+    finally:
+        if tmp:
+            D.close()
+
+
+# ------------------------------------------------------------------------------------ greedy sparse Bayesian learning
+def _fsbl_knobs(who, A, b, sigma2, caps, min_increase, alpha):
+    M, N, _ = _meta(A)
+    if isinstance(sigma2, (bool, np.bool_)):  # the reference's rmps(A, b, Val(true), ...)
+        raise NotImplementedError(f"{who}: the σ²-optimising form (Val(true)) is not served: pass the scalar noise variance σ²")
+    if np.ndim(sigma2) != 0:
+        raise NotImplementedError(f"{who}: only a scalar noise variance σ² is served, not a covariance matrix Σ")
+    if not (sigma2 > 0 and np.isfinite(sigma2)):
+        raise ValueError(f"σ² = {sigma2} has to be positive and finite")
+    if not min_increase >= 0:
+        raise ValueError(f"min_increase = {min_increase} has to be non-negative")
+    for name, c in caps.items():
+        if c is not None and (not _is_int(c) or c < 1):
+            raise ValueError(f"{name} = {c} has to be at least 1")
+    if np.shape(b) != (M,):
+        raise ValueError(f"DimensionMismatch: size(A, 1) = {M} != {np.shape(b)} = size(b)")
+    if alpha is not None:
+        alpha = np.asarray(alpha, dtype=np.float64)
+        if alpha.shape != (N,) or not np.all(alpha > 0):
+            raise ValueError("every entry of alpha has to be positive, or +inf for an inactive atom")
+    return M, N
+
+
+def fsbl(A, b, sigma2, *, maxiter=None, min_increase=1e-6, alpha=None, return_info=False):
+    """fsbl(A, b, σ²; maxiter = 2 size(A, 2), min_increase = 1e-6) (src/sbl.jl:149-176): fast sparse Bayesian learning for a scalar noise
+    variance.  Every pass changes the prior precision α_i of the ONE atom whose addition, deletion or re-estimation raises the marginal
+    likelihood most; the loop stops after the pass in which that increase is below min_increase, at the latest after maxiter passes
+    (converged is then False; no error).  Returns x, Float64[N]: exactly 0 off the active set, Q_j / α_j on it -- the reference's solve
+    (A_aᵀA_a/σ² + diag α_a) x_a = A_aᵀb/σ² in exact arithmetic (include/csmp.h, csmp_fsbl).  alpha: prior precisions to start from
+    (+inf: inactive).  return_info=True: (x, info) with info = {iterations, converged, alpha, history}; history lists the applied steps
+    as (action, index), 1 add, 2 delete, 3 re-estimate.  A noise covariance matrix raises NotImplementedError."""
+    _fsbl_knobs("fsbl", A, b, sigma2, {"maxiter": maxiter}, min_increase, alpha)
+    D, tmp = _dict(A)
+    try:
+        x, info = D.ctx.fsbl(b, float(sigma2), maxiter, float(min_increase), alpha)
+        return (x, info) if return_info else x
+    finally:
+        if tmp:
+            D.close()
+
+
+def rmps(A, b, sigma2, *, maxiter=None, maxiter_acquisition=None, maxiter_deletion=None, min_increase=1e-6, alpha=None, return_info=False):
+    """rmps(A, b, σ²; maxiter, maxiter_acquisition, maxiter_deletion = size(A, 1), min_increase = 1e-6) (src/sbl.jl:373-437): relevance
+    matching pursuit for a scalar noise variance.  An outer iteration adds atoms while an addition raises the marginal likelihood, then
+    deletes the active atom of least q²/s while that is below 1 and otherwise re-estimates the α_i that gains most, until that gain is
+    below min_increase; it ends when α no longer changes.  x, alpha, return_info: as fsbl; info["iterations"] counts the applied steps.
+    A noise covariance matrix and the σ²-optimising form (σ² = True, the reference's Val(true)) raise NotImplementedError."""
+    _fsbl_knobs("rmps", A, b, sigma2, {"maxiter": maxiter, "maxiter_acquisition": maxiter_acquisition, "maxiter_deletion": maxiter_deletion},
+                min_increase, alpha)
+    D, tmp = _dict(A)
+    try:
+        x, info = D.ctx.rmps(b, float(sigma2), maxiter, maxiter_acquisition, maxiter_deletion, float(min_increase), alpha)
         return (x, info) if return_info else x
     finally:
         if tmp:
@@ -934,6 +993,50 @@ class SBL(_Update):
 
 
 SparseBayesianLearning = SBL
+
+
+class FSBL(_Update):
+    """FSBL(A, b, σ²) = FastSparseBayesianLearning (src/sbl.jl:60-87) for a scalar noise variance; update!(P): :165-176, one pass of
+    csmp_fsbl (maxiter = 1) warm-started from the kept prior precisions.  `alpha` is a torch CUDA Float64 tensor, +inf (all atoms
+    inactive) at the start; `x` is the posterior mean of the current α.  C⁻¹, S and Q are not kept between the calls: every call REPLAYS
+    the active set -- one rank-one step per active atom -- before its pass, so a call costs (active atoms + 1) steps.  t calls give the
+    history of fsbl(A, b, σ², maxiter=t)."""
+
+    def __init__(self, A, b, sigma2):
+        _fsbl_knobs("FSBL", A, b, sigma2, {}, 0.0, None)
+        import torch
+        self.D, self._tmp = _dict(A)
+        self.A, self.b, self.sigma2 = A, np.asarray(b), float(sigma2)
+        N = self.D.shape[1]
+        self.ctx = self.D.ctx.clone()  # a context of its own that borrows the resident dictionary, as the pursuit functors
+        self._bd = torch.from_numpy(self.ctx._b(b)).cuda()
+        self.alpha = torch.full((N,), float("inf"), dtype=torch.float64, device="cuda")
+        self._xd = torch.zeros(N, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()  # (the library works on a stream of its own)
+        self.iterations = 0
+        self.history = []
+
+    def update_(self, x=None):
+        info = self.ctx.fsbl_device(self._bd, self.sigma2, self._xd, self.alpha, self.alpha, maxiter=1, min_increase=0.0, history_cap=1)
+        self.iterations += 1
+        self.history += info["history"]
+        out = self._xd.cpu().numpy()
+        if x is None:
+            return out
+        x[:] = out
+        return x
+
+    @property
+    def x(self):
+        return self._xd.cpu().numpy()
+
+    def close(self):
+        self.ctx.close()
+        if self._tmp:
+            self.D.close()
+
+
+FastSparseBayesianLearning = FSBL
 
 
 class _TwoStage(_Update):

@@ -22,6 +22,7 @@
 #include "csmp_bp.hpp"
 #include "csmp_bpd.hpp"
 #include "csmp_sbl.hpp"
+#include "csmp_fsbl.hpp"
 
 #include <algorithm>
 #include <iterator>
@@ -62,5 +63,6 @@ using namespace csmp;
 #include "host/bp.hpp"
 #include "host/bpd.hpp"
 #include "host/sbl.hpp"
+#include "host/fsbl.hpp"
 #include "host/measure.hpp"
 #include "host/rccl.hpp"

@@ -207,6 +207,19 @@ struct SblBuf {
     int64_t cps = 0;
 };
 
+// greedy sparse Bayesian learning (csmp_fsbl.hpp, host/fsbl.hpp): Ci = C^-1 (M columns of the even leading dimension ldc), the M-vectors
+// a_i and v = C^-1 a_i (Mp doubles each, zero beyond M: the sweep reads Mv rows), the N-vectors alpha, S, Q, w = A'v and x, the partials
+// of the N-pass and the decision record, made on first use, sized by the dictionary: all of them, or none.  Apart from SblBuf, BpBuf and
+// BpdBuf: nothing here is kept from one call to the next but the memory.
+struct FsblBuf {
+    double *Ci = nullptr, *vec = nullptr, *alpha = nullptr, *S = nullptr, *Q = nullptr, *w = nullptr, *x = nullptr, *pval = nullptr;
+    long long* pidx = nullptr;
+    FsblRec* rec = nullptr;
+    int M = 0, Mp = 0;  // rows the buffers were made for (0: none), and the length of each of the two M-vectors in vec
+    int64_t N = 0;      // ... and atoms
+    int64_t ldc = 0;
+};
+
 struct csmp_ctx;
 // Subspace Pursuit as a resumable job: see host/gomp_sp.hpp
 struct SpJob {
@@ -280,6 +293,7 @@ struct csmp_ctx {
     int tune_swap_refuse = 0;  // csmp_tune: OMPR's inverse-Gram exchanges fail their guard (tests walk the fallback to the QR path)
     int tune_rowgram_scalar = 0;  // csmp_tune: k_rowgram without 16-byte loads
     int tune_sbl_scalar = 0;      // csmp_tune: csmp_sbl's weighted k_rowgram and k_sbl_forms without 16-byte loads
+    int tune_fsbl_scalar = 0;     // csmp_tune: k_fsbl_col without 16-byte loads
     int tune_pass_c = 0;      // csmp_tune: 1 = the grouped OMP scheduler's passes store c, which nothing reads (shared_pass_launch)
     int tune_group_split = 0; // csmp_tune: how the grouped scheduler cuts a batch into wide groups, narrow_last_groups' split (1 = evenly)
     int tune_diag_split = 0;  // csmp_tune: fused kernels run as one launch per part (a kernel trace then shows the parts)
@@ -319,6 +333,7 @@ struct csmp_ctx {
     BpBuf bp;
     BpdBuf bpd;
     SblBuf sbl;
+    FsblBuf fsbl;
     // profiling
     bool prof = false;
     int prof_every = 1;       // time every n-th sweep launch only (an event pair costs a few us of stream time)

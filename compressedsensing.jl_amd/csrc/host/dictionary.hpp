@@ -250,6 +250,7 @@ static int dict_forget(csmp_ctx* ctx) {
     bp_free(ctx->bp);
     bpd_free(ctx->bpd);
     sbl_free(ctx->sbl);
+    fsbl_free(ctx->fsbl);
     return CSMP_OK;
 }
 

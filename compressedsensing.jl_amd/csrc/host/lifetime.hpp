@@ -118,6 +118,11 @@ static void sbl_free(SblBuf& t) {
     t = SblBuf();
 }
 
+static void fsbl_free(FsblBuf& t) {
+    dfree(t.Ci); dfree(t.vec); dfree(t.alpha); dfree(t.S); dfree(t.Q); dfree(t.w); dfree(t.x); dfree(t.pval); dfree(t.pidx); dfree(t.rec);
+    t = FsblBuf();
+}
+
 static void dict_release(csmp_ctx* ctx) {
     if (ctx->share && --ctx->share->refs == 0) {
         if (ctx->share->kind == 0) (void)hipFree(ctx->share->p);
@@ -146,6 +151,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     bp_free(ctx->bp);
     bpd_free(ctx->bpd);
     sbl_free(ctx->sbl);
+    fsbl_free(ctx->fsbl);
     if (ctx->comm) (void)csmp_comm_free(ctx);
     for (auto& t : ctx->twins) {
         if (t) (void)csmp_destroy(t);

@@ -273,6 +273,7 @@ extern "C" int csmp_tune(csmp_ctx* ctx, int key, int64_t value) {
         case CSMP_TUNE_FAIL_ALLOC: ctx->tune_fail_alloc = (int)value; return CSMP_OK;
         case CSMP_TUNE_ROWGRAM_SCALAR: ctx->tune_rowgram_scalar = value == 1 ? 1 : 0; return CSMP_OK;
         case CSMP_TUNE_SBL_SCALAR: ctx->tune_sbl_scalar = value == 1 ? 1 : 0; return CSMP_OK;
+        case CSMP_TUNE_FSBL_SCALAR: ctx->tune_fsbl_scalar = value == 1 ? 1 : 0; return CSMP_OK;
         case CSMP_TUNE_PASS_C: ctx->tune_pass_c = value == 1 ? 1 : 0; return CSMP_OK;
         case CSMP_TUNE_GROUP_SPLIT:
             if (value > 3) return fail(ctx, CSMP_EINVAL, "csmp_tune: group_split must be 0 (a narrow last group where it costs no pass), 1 (even), 2 or 3 (measurements)");

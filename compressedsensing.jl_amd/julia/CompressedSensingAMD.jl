@@ -311,7 +311,7 @@ bpd_ard(A::MatOrDict, b::AbstractVector, δ::Real, ε::Real = δ^2; maxiter::Int
 
 # ---------------------------------------------------------------------------------- sparse Bayesian learning
 # src/sbl.jl:1-51: sbl(A, b, σ²) and SBL(A, b, σ²) with update! for a SCALAR noise variance, in the Woodbury form on the M × M matrix
-# σ² I + A Γ Aᵀ (csmp_sbl, include/csmp.h).  A noise covariance matrix Σ is not served, nor are fsbl and rmps.
+# σ² I + A Γ Aᵀ (csmp_sbl, include/csmp.h).  A noise covariance matrix Σ is not served; fsbl and rmps follow below.
 const CSMP_SBL_CONVERGED = 1
 function sbl_call(D::Dictionary, b::AbstractVector, σ²::Real, γ::Vector{Float64}, maxiter::Int, min_change::Real)
     bb, bt = bvec(b)
@@ -343,6 +343,50 @@ function update!(S::SparseBayesianLearning, x::AbstractVector = zeros(length(S.g
     return x
 end
 (S::SparseBayesianLearning)(x::AbstractVector = zeros(length(S.gamma))) = update!(S, x)
+
+# ---------------------------------------------------------------------------------- greedy sparse Bayesian learning
+# src/sbl.jl:57-437: fsbl(A, b, σ²) and rmps(A, b, σ²) for a SCALAR noise variance (csmp_fsbl, csmp_rmps, include/csmp.h): every step
+# changes the prior precision α_i of one atom.  x is exactly zero off the active set.  alpha: prior precisions to start from (Inf =
+# inactive).  return_info: (x, info) with the history of applied steps as (action, index) pairs, 1 add, 2 delete, 3 re-estimate, the
+# index 1-based.  A covariance matrix and the σ²-optimising rmps(A, b, Val(true)) are refused.
+const CSMP_FSBL_CONVERGED = 1
+const CSMP_RMPS_CONVERGED = 1
+greedy_info(it, flags, α, hist, n) = (iterations = Int(it[]), converged = flags[] & CSMP_FSBL_CONVERGED != 0, alpha = α,
+                                      history = [(Int(hist[1, t]), Int(hist[2, t]) + 1) for t in 1:n])
+function fsbl(A::MatOrDict, b::AbstractVector, σ²::Real; maxiter::Int = 2size(A, 2), min_increase::Real = 1e-6,
+              alpha::Union{Nothing, AbstractVector} = nothing, return_info::Bool = false)
+    D = dict(A)
+    bb, bt = bvec(b)
+    xd = zeros(Float64, size(D, 2))
+    α = alpha === nothing ? fill(Inf, size(D, 2)) : convert(Vector{Float64}, alpha)
+    cap = max(maxiter, 1)
+    hist = zeros(Int64, 2, cap)
+    it, flags = Ref{Int64}(0), Ref{Cint}(0)
+    GC.@preserve bb α xd hist check(D, ccall((:csmp_fsbl, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Int64, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Int64}, Int64, Ref{Int64}, Ref{Cint}),
+        D.ctx, bb, bt, σ², maxiter, min_increase, α, xd, α, CSMP_HOST, hist, cap, it, flags))
+    x = sparse(xd)
+    return return_info ? (x, greedy_info(it, flags, α, hist, count(!iszero, view(hist, 1, :)))) : x
+end
+function rmps(A::MatOrDict, b::AbstractVector, σ²::Real; maxiter::Int = size(A, 1), maxiter_acquisition::Int = size(A, 1),
+              maxiter_deletion::Int = size(A, 1), min_increase::Real = 1e-6, alpha::Union{Nothing, AbstractVector} = nothing,
+              return_info::Bool = false, history_cap::Int = 4size(A, 2))
+    D = dict(A)
+    bb, bt = bvec(b)
+    xd = zeros(Float64, size(D, 2))
+    α = alpha === nothing ? fill(Inf, size(D, 2)) : convert(Vector{Float64}, alpha)
+    hist = zeros(Int64, 2, max(history_cap, 1))
+    it, flags = Ref{Int64}(0), Ref{Cint}(0)
+    GC.@preserve bb α xd hist check(D, ccall((:csmp_rmps, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Int64, Int64, Int64, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Int64}, Int64,
+         Ref{Int64}, Ref{Cint}),
+        D.ctx, bb, bt, σ², maxiter, maxiter_acquisition, maxiter_deletion, min_increase, α, xd, α, CSMP_HOST, hist, max(history_cap, 0), it, flags))
+    x = sparse(xd)
+    return return_info ? (x, greedy_info(it, flags, α, hist, min(Int(it[]), max(history_cap, 0)))) : x
+end
+fsbl(A::MatOrDict, b::AbstractVector, Σ::AbstractMatrix; kwargs...) = error("fsbl: only a scalar noise variance σ² is served, not a covariance matrix")
+rmps(A::MatOrDict, b::AbstractVector, Σ::AbstractMatrix; kwargs...) = error("rmps: only a scalar noise variance σ² is served, not a covariance matrix")
+rmps(A::MatOrDict, b::AbstractVector, ::Val{true}, args...; kwargs...) = error("rmps: the σ²-optimising form is not served: pass the noise variance σ²")
 
 # ---------------------------------------------------------------------------------- dictionary analysis
 # src/util.jl:2,96-115: colnorms, coherence, babel, cumbabel.  The inner products are raw, as in the reference (which assumes unit-norm

@@ -511,7 +511,7 @@ int csmp_bpd_reweighted(csmp_ctx *ctx, const void *b, int b_dtype, double delta,
 
 /* ------------------------------------------------------------------ sparse Bayesian learning
  * sbl(A, b, sigma2) and update!(::SBL): src/sbl.jl:1-51, for a scalar noise variance sigma2 (a matrix Sigma is not served; fsbl and
- * rmps, :57-470, are not served either).  The reference factorises the N x N matrix A'A / sigma2 + Gamma^-1 in every update; this is
+ * rmps, :57-437, are csmp_fsbl and csmp_rmps below).  The reference factorises the N x N matrix A'A / sigma2 + Gamma^-1 in every update; this is
  * the same update in the Woodbury form, on the M x M matrix
  *     C = sigma2 I + A Gamma A' = L L',   Gamma = diag(gamma)
  * -- positive definite for EVERY dictionary, so size(A,1) > size(A,2) is served.  For every atom j
@@ -539,6 +539,48 @@ int csmp_bpd_reweighted(csmp_ctx *ctx, const void *b, int b_dtype, double delta,
 #define CSMP_SBL_CONVERGED 1
 int csmp_sbl(csmp_ctx *ctx, const void *b, int b_dtype, double sigma2, int64_t maxiter, double min_change,
              const double *gamma_in, double *x, double *gamma_out, int loc, int64_t *iterations, int *flags);
+
+/* ------------------------------------------------------------------ greedy sparse Bayesian learning
+ * fsbl(A, b, sigma2) and rmps(A, b, sigma2): src/sbl.jl:57-437, for a scalar noise variance sigma2 (a matrix Sigma, the sigma2-optimising
+ * rmps and the unused rmp_acquisition_value are not served).  Every step changes the prior precision alpha_i of ONE atom (+inf =
+ * inactive; all atoms start there).  The state is alpha, C^-1 (size(A,1)^2 doubles, I / sigma2 at the start),
+ *     S_j = a_j' C^-1 a_j   and   Q_j = a_j' C^-1 b      (|a_j|^2 / sigma2 and (A'b)_j / sigma2 at the start),
+ * and per atom f = alpha / (alpha - S) (1 where inactive), s = S f, q = Q f, relevant = s < q^2, alpha* = s^2 / (q^2 - s).  The actions on
+ * a picked atom i: add (alpha_i = alpha*, gam = 1 / alpha*), delete (gam = -1 / alpha_i, alpha_i = +inf), re-estimate (gam = 1 / alpha* -
+ * 1 / alpha_i, alpha_i = alpha*), each followed by the rank-one step
+ *     v = C^-1 a_i;  den = 1 / gam + S_i;  C^-1 -= v v' / den;  w = A'v;  S -= w^2 / den;  Q -= w Q_i / den.
+ * One step is an N-pass that applies the previous step's S / Q update and evaluates every atom, ONE host read (the decision), one
+ * M x M matrix-vector product, one streaming update of C^-1 and one product sweep over A.
+ * csmp_fsbl, a pass (:165-176): delta_j = delta_add (inactive, relevant), delta_del (active, not relevant), delta_upd (active, relevant)
+ * or 0; i = the first arg-max; where delta_i > 0 the matching action.  After the pass in which max delta < min_increase the loop stops
+ * (the reference's default: 1e-6), at the latest after maxiter passes (the reference's default: 2 size(A,2)); reaching maxiter is not an
+ * error.  maxiter = 1 is update!(::FSBL): alpha_out of one call is the alpha_in of the next.
+ * csmp_rmps, an outer iteration (:389-404): at most maxiter_acquisition additions of the first arg-max of delta_add while it is > 0; stop
+ * where alpha has not changed since the last check; at most maxiter_deletion turns, each the deletion of the first arg-min of q^2 / s over
+ * the active atoms that are not relevant where that is < 1, else the re-estimation of the arg-max of delta_upd where that is > 0, the
+ * stage ending once that value (0 where nothing was done) is < min_increase; stop where alpha has not changed.  The reference's defaults:
+ * size(A,1) for the three caps.
+ * x: the posterior mean, Float64[size(A,2)], exactly 0 on the inactive atoms and Q_j / alpha_j on the active ones -- in exact arithmetic
+ * what the reference's solve (A_a'A_a / sigma2 + diag alpha_a) x_a = A_a'b / sigma2 gives.  alpha_in (may be NULL: all +inf): a warm
+ * start, entries positive or +inf; the state is rebuilt from I / sigma2 by one rank-one step per finite entry, in index order.  alpha_out
+ * (may be NULL; may be alpha_in).  loc says where b, x, alpha_in and alpha_out live: CSMP_HOST, or CSMP_DEVICE (the call still returns
+ * with the work done).  history (host memory, may be NULL): the pairs (action, index) of the applied steps, the first history_cap of
+ * them, 2 history_cap words; actions: 1 add, 2 delete, 3 re-estimate.  iterations: passes done (csmp_fsbl), steps applied (csmp_rmps).
+ * flags: CSMP_FSBL_CONVERGED / CSMP_RMPS_CONVERGED -- a stopping rule ended the run, not a cap.  iterations, flags: may be NULL.
+ * Memory, kept by the context until csmp_set_dictionary, apart from csmp_sbl's buffers and csmp_bp's and csmp_bpd's factors (no call here
+ * reads or invalidates them): C^-1, size(A,1)^2 doubles -- 128 MiB at 4096 rows -- and five vectors of size(A,2) doubles.
+ * CSMP_EINVAL: null pointers, a b_dtype / loc that is neither, sigma2 not positive and finite, min_increase negative or NaN, a cap < 1,
+ * an entry of alpha_in that is not positive (or NaN), and a value of the marginal likelihood's change that is not finite.  CSMP_ERANGE:
+ * more than 2^19 rows.  CSMP_ESTATE: no dictionary -- and a host-streamed dictionary (CSMP_HOST_STREAMED), as csmp_sbl.  CSMP_ENOMEM:
+ * the size(A,1)^2 doubles of C^-1 or a vector could not be allocated; none of them is left behind, and the next call starts afresh. */
+#define CSMP_FSBL_CONVERGED 1
+#define CSMP_RMPS_CONVERGED 1
+int csmp_fsbl(csmp_ctx *ctx, const void *b, int b_dtype, double sigma2, int64_t maxiter, double min_increase,
+              const double *alpha_in, double *x, double *alpha_out, int loc,
+              int64_t *history, int64_t history_cap, int64_t *iterations, int *flags);
+int csmp_rmps(csmp_ctx *ctx, const void *b, int b_dtype, double sigma2, int64_t maxiter, int64_t maxiter_acquisition,
+              int64_t maxiter_deletion, double min_increase, const double *alpha_in, double *x, double *alpha_out, int loc,
+              int64_t *history, int64_t history_cap, int64_t *iterations, int *flags);
 
 /* ------------------------------------------------------------------ dictionary analysis
  * colnorms(A): src/util.jl:2.  norms[j] = ||a_j||_2 of every column of the resident dictionary, N doubles, to host memory

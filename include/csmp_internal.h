@@ -55,6 +55,22 @@ int csmp_sbl_forms(csmp_ctx *ctx, const double *W, int64_t ldw, const double *t,
  * events: the weighted Gram matrix and its reduction; the assembly, the factorisation, L^-T and t = L^-1 b; k_sbl_forms.  The averages
  * (ms) of `reps` runs after one warm-up run; gamma is not updated.  Any pointer may be NULL.  CSMP_ESTATE: no such call has been made. */
 int csmp_bench_sbl(csmp_ctx *ctx, double sigma2, int reps, double *gram_ms, double *factor_ms, double *forms_ms);
+/* k_fsbl_score and k_fsbl_pick alone (the N-pass of a csmp_fsbl / csmp_rmps step) on a state of the caller's: alpha (+inf = inactive), S
+ * and Q, size(A,2) doubles each in host memory.  mode: 1 fsbl's delta, 2 the acquisition value, 3 rmps' deletion value (the MINIMUM is
+ * picked), 4 the update value.  values: every atom's value, size(A,2) doubles; pick, value: the first arg-max (arg-min) and its value;
+ * action: what the drivers would apply to it, 0 nothing, 1 add, 2 delete, 3 re-estimate.  pick, value and action may be NULL.
+ * CSMP_EINVAL: a value that is NaN, or an infinite maximum. */
+int csmp_fsbl_score(csmp_ctx *ctx, const double *alpha, const double *S, const double *Q, int mode, double *values, int64_t *pick,
+                    double *value, int *action);
+/* the rank-one step sqc(i, gamma) alone -- k_fsbl_col, v = C^-1 a_i, k_fsbl_rank1, w = A'v and the S / Q update of the next N-pass -- on a
+ * state of the caller's, updated in place in host memory: Cinv, size(A,1)^2 doubles, column-major and symmetric; S and Q, size(A,2)
+ * doubles.  gamma: the change of atom i's prior variance, finite and not zero. */
+int csmp_fsbl_sqc(csmp_ctx *ctx, double *Cinv, double *S, double *Q, int64_t i, double gamma);
+/* the parts of one greedy step on the state the LAST csmp_fsbl / csmp_rmps call of this context left behind, each bracketed by HIP
+ * events: the N-pass with the pending S / Q update and the pick; the column and v = C^-1 a_i; the rank-one update of C^-1; the product
+ * sweep w = A'v.  Every run adds the prior variance 1 to atom 0.  The averages (ms) of `reps` runs after one warm-up run.  Any pointer may
+ * be NULL.  CSMP_ESTATE: no such call has been made. */
+int csmp_bench_fsbl(csmp_ctx *ctx, int reps, double *score_ms, double *colgemv_ms, double *rank1_ms, double *sweep_ms);
 /* what configure_sweep chose for the resident dictionary: loads per unit of k_sweep_gen (16 / 8 / 4); phases the residual is
  * staged in (1: one LDS image); workgroups of a stand-alone sweep and of the sweep inside the tick kernel; dynamic LDS bytes;
  * dynamic = 1: the columns are handed out at run time (k_sweep_dyn and the DYN tick), 0: split statically; columns_per_unit: 2 or 4
@@ -77,7 +93,8 @@ int csmp_sweep_group_wide(const csmp_ctx *ctx, int *group_wide);
 #define CSMP_TUNE_GROUP_WIDE 21   /* 1: no wide groups (every pass serves at most group_max signals); 2: wide groups, the three of a round on ONE pipeline (a measurement: slower); default 0: batches of more signals than that run groups of up to 2 * group_max wherever the grouped scheduler has group_max = 4 images per workgroup on a Float32 dictionary and CSMP_TUNE_GROUP_MAX is 0.  CSMP_TUNE_TICK_GRID overrides the wide pass's grid too, rounded down to a multiple of 16 */
 #define CSMP_TUNE_ROWGRAM_SCALAR 22 /* 1: k_rowgram (csmp_bp, csmp_bp_rowgram) loads the dictionary with scalar loads, as for columns that start on no 16-byte boundary (the library's own copy always does: tests reach that instantiation here); the same bits */
 #define CSMP_TUNE_SBL_SCALAR 25   /* 1: csmp_sbl's kernels that read the dictionary (the weighted k_rowgram, k_sbl_forms; csmp_sbl_rowgram and csmp_sbl_forms too) load it with scalar loads, as for columns that start on no 16-byte boundary; the same bits */
-#define CSMP_TUNE_PASS_C 23       /* 1: the shared passes of csmp_omp_batch's grouped scheduler store every member's c = A'r, which nothing reads there; default 0: they store none (csmp_mp_batch's passes always do).  The same results */
+#define CSMP_TUNE_FSBL_SCALAR 26  /* 1: k_fsbl_col (csmp_fsbl, csmp_rmps, csmp_fsbl_sqc) loads the picked column with scalar loads, as for columns that start on no 16-byte boundary; the same bits */
+#define CSMP_TUNE_PASS_C 23      /* 1: the shared passes of csmp_omp_batch's grouped scheduler store every member's c = A'r, which nothing reads there; default 0: they store none (csmp_mp_batch's passes always do).  The same results */
 #define CSMP_TUNE_GROUP_SPLIT 24  /* how the grouped scheduler cuts a batch into WIDE groups (host/batch_plan.hpp: narrow_last_groups).  Default 0: ceil(nsig / group_wide) groups, the last one of group_max signals -- a narrow pass -- where that takes no pass more (18 signals: 8 + 6 + 4); 1: as even as possible (6 + 6 + 6); 2, 3: measurements (7 + 7 + 4, 8 + 8 + 2).  The same results */
 #define CSMP_TUNE_TICK_ORDER 10   /* 1: the tick kernel's sweep workgroups are dispatched ahead of its append stages' */
 #define CSMP_TUNE_CLAIM_POOLS 11  /* the dynamic sweep: column pools a workgroup may claim from (its own first) */
