@@ -313,6 +313,38 @@ def bp(A, b, w=None, *, rho=1.0, maxiter=16384, tol=1e-8, check_every=32, return
 basispursuit = bp
 
 
+def bp_batch(A, B, w=None, *, rho=1.0, maxiter=16384, tol=1e-8, check_every=32, return_info=False):
+    """[bp(A, B[:, s], w) for s in axes(B, 2)] on one GPU: up to eight signals take their ADMM iterations in lockstep, so the dictionary,
+    R⁻¹, R⁻ᵀ and G = A Aᵀ are read once per step for all of them; a finished signal's place is taken by the next column.  Every result is
+    bp's bit for bit.  The weights are shared by all signals.  Returns a list of SparseVectors; return_info=True: (list, info) with
+    info = {iterations int64[nsig], converged bool[nsig], resnorm float64[nsig], factored}."""
+    M, N = _bp_knobs(A, rho, maxiter, tol, check_every)
+    w = np.ones(1) if w is None else np.atleast_1d(np.asarray(w, dtype=np.float64))
+    if w.ndim != 1 or len(w) not in (1, N):
+        raise ValueError(f"length(w) = {w.shape} but size(A, 2) = {N}")
+    if not np.all((w >= 0) & np.isfinite(w)):
+        raise ValueError("the weights have to be non-negative and finite")
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] != M:
+        raise ValueError(f"size(B) = {B.shape} but size(A, 1) = {M}: B holds one signal per column")
+    D, tmp = _dict(A)
+    try:
+        try:
+            X, info = D.ctx.bp_batch(B, w, float(rho), int(maxiter), float(tol), int(check_every))
+        except CsmpError as e:
+            if e.code == _lib.EINVAL and "positive definite" in str(e):
+                raise ValueError(str(e)) from None
+            raise
+        xs = []
+        for s in range(X.shape[1]):
+            nz = np.flatnonzero(X[:, s])
+            xs.append(SparseVector(N, nz, X[nz, s]))
+        return (xs, info) if return_info else xs
+    finally:
+        if tmp:
+            D.close()
+
+
 def _bp_reweighted(A, b, scheme, eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights, ard_iter=8):
     M, N = _bp_knobs(A, rho, inner_maxiter, tol, check_every)
     if not (eps > 0 and np.isfinite(eps)):

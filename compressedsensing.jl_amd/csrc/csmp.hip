@@ -61,6 +61,8 @@ using namespace csmp;
 #include "host/analysis.hpp"
 #include "host/reweight.hpp"
 #include "host/bp.hpp"
+#include "host/bp_batch_plan.hpp"
+#include "host/bp_batch.hpp"
 #include "host/bpd.hpp"
 #include "host/sbl.hpp"
 #include "host/fsbl.hpp"

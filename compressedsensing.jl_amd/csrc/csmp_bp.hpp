@@ -12,6 +12,8 @@
 //   k_bp_start / k_bp_pq   the M-vector steps
 //   k_bp_update        the element-wise step over the N atoms, the list of z+ (k_ista_update's layout), the residual norms' partials
 //   k_bp_fold          the partials added in segment order
+//   k_bp_gemm          k_bp_gemv for up to eight right-hand sides per read of the matrix, and the group forms k_bp_update_group,
+//                      k_ista_axpy_group, k_ista_resum_group, k_bp_pq_group: csmp_bp_batch's step for all live members (host/bp_batch.hpp)
 //
 // Determinism: no atomics, no workgroup waits for another, every sum has a fixed order: the same bits on every run.
 #pragma once
@@ -223,6 +225,55 @@ __global__ __launch_bounds__(256) void k_bp_gemv(const double* __restrict__ mat,
     if (lane == 0) out[c] = a;
 }
 
+// k_bp_gemv for the L right-hand sides of one step of csmp_bp_batch (host/bp_batch.hpp):  out_m[c] = sum_t mat[t, c] x_m[t],  m < L.
+// A wave per output column as above; a lane loads its matrix elements ONCE and feeds each to L fmas, so a launch's traffic from
+// memory is one pass over the triangle or the square whatever L is (the L vectors, L M doubles, stay in the caches).  For every pair
+// (c, m) the operations are k_bp_gemv's and nothing else -- the lane partials over t = lo + lane in steps of 128 on the chains a0 and
+// a1, the tail into a0, a0 + a1, the butterfly 32 .. 1 -- so every out_m has k_bp_gemv's bits; L = 1 is k_bp_gemv.
+// 2 L accumulators per column, 2 + 2 L loads in flight per lane and trip, no LDS, no scratch.
+constexpr int kBpGemmMax = 8;
+struct BpGemm {
+    const double* x[kBpGemmMax];
+    double* out[kBpGemmMax];
+};
+template <int L>
+__global__ __launch_bounds__(256) void k_bp_gemm(const double* __restrict__ mat, int64_t ld, int M, int mode, const BpGemm g) {
+    static_assert(L >= 1 && L <= kBpGemmMax, "right-hand sides of a launch");
+    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= M) return;
+    const int lo = mode == BP_LOWER ? c : 0, hi = mode == BP_UPPER ? c + 1 : M;
+    const double* col = mat + (int64_t)c * ld;
+    double a0[L], a1[L];
+#pragma unroll
+    for (int m = 0; m < L; ++m) a0[m] = a1[m] = 0.0;
+    int t = lo + lane;
+    for (; t + 64 < hi; t += 128) {
+        const double m0 = col[t], m1 = col[t + 64];
+        double x0[L], x1[L];
+#pragma unroll
+        for (int m = 0; m < L; ++m) {
+            x0[m] = g.x[m][t];
+            x1[m] = g.x[m][t + 64];
+        }
+#pragma unroll
+        for (int m = 0; m < L; ++m) {
+            a0[m] = fma(m0, x0[m], a0[m]);
+            a1[m] = fma(m1, x1[m], a1[m]);
+        }
+    }
+    if (t < hi) {
+        const double m0 = col[t];
+#pragma unroll
+        for (int m = 0; m < L; ++m) a0[m] = fma(m0, g.x[m][t], a0[m]);
+    }
+#pragma unroll
+    for (int m = 0; m < L; ++m) {
+        double a = a0[m] + a1[m];
+        for (int s = 32; s >= 1; s >>= 1) a += shx(a, s);
+        if (lane == 0) g.out[m][c] = a;
+    }
+}
+
 // the start from z = u = 0:  p = q = 0,  e = -b
 __global__ __launch_bounds__(256) void k_bp_start(const double* __restrict__ b, int M, double* __restrict__ p, double* __restrict__ q,
                                                   double* __restrict__ e) {
@@ -232,10 +283,10 @@ __global__ __launch_bounds__(256) void k_bp_start(const double* __restrict__ b, 
     q[i] = 0.0;
     e[i] = -b[i];
 }
-// p+ = b - r;  q+ = p - g - p+ (g = G y);  and the next iteration's  e = p+ - q+ - b
-__global__ __launch_bounds__(256) void k_bp_pq(const double* __restrict__ b, const double* __restrict__ r, const double* __restrict__ g, int M,
-                                               double* __restrict__ p, double* __restrict__ q, double* __restrict__ e) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
+// p+ = b - r;  q+ = p - g - p+ (g = G y);  and the next iteration's  e = p+ - q+ - b.  blk: the workgroup's 256 rows.
+__device__ __forceinline__ void bp_pq_body(const int blk, const double* __restrict__ b, const double* __restrict__ r, const double* __restrict__ g,
+                                           int M, double* __restrict__ p, double* __restrict__ q, double* __restrict__ e) {
+    const int i = blk * 256 + threadIdx.x;
     if (i >= M) return;
     const double pn = b[i] - r[i];
     const double qn = p[i] - g[i] - pn;
@@ -243,18 +294,23 @@ __global__ __launch_bounds__(256) void k_bp_pq(const double* __restrict__ b, con
     q[i] = qn;
     e[i] = pn - qn - b[i];
 }
+__global__ __launch_bounds__(256) void k_bp_pq(const double* __restrict__ b, const double* __restrict__ r, const double* __restrict__ g, int M,
+                                               double* __restrict__ p, double* __restrict__ q, double* __restrict__ e) {
+    bp_pq_body((int)blockIdx.x, b, r, g, M, p, q, e);
+}
 
 // t = z - c;  z+ = sign(t) max(|t| - w / rho, 0);  u+ = t - z+.  The list is that of z+, in k_ista_update's layout (segments of seg_len
 // atoms, one workgroup each, seg_cnt): k_ista_axpy consumes it unchanged.  rpart[s] = the segment's share of |u+ - u|^2,
 // rpart[kIstaMaxSegs + s] of |z+ - z|^2 (thread partials in index order, then block_sum256).
-__global__ __launch_bounds__(kIstaThreads) void k_bp_update(const double* __restrict__ c, const double* __restrict__ w, int64_t nw, double rho,
-                                                            double* __restrict__ z, double* __restrict__ u, int64_t N, int64_t seg_len,
-                                                            int* __restrict__ lidx, double* __restrict__ lval, int* __restrict__ seg_cnt,
-                                                            double* __restrict__ rpart) {
+// (seg: the workgroup's segment)
+__device__ __forceinline__ void bp_update_body(const int seg, const double* __restrict__ c, const double* __restrict__ w, int64_t nw, double rho,
+                                               double* __restrict__ z, double* __restrict__ u, int64_t N, int64_t seg_len,
+                                               int* __restrict__ lidx, double* __restrict__ lval, int* __restrict__ seg_cnt,
+                                               double* __restrict__ rpart) {
     __shared__ int wcnt[kIstaThreads / kWave];
     __shared__ double red[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t j0 = (int64_t)blockIdx.x * seg_len, j1 = j0 + seg_len < N ? j0 + seg_len : N;
+    const int64_t j0 = (int64_t)seg * seg_len, j1 = j0 + seg_len < N ? j0 + seg_len : N;
     const double w0 = w[0];
     double sp = 0.0, sd = 0.0;
     int64_t base = j0;
@@ -294,10 +350,57 @@ __global__ __launch_bounds__(kIstaThreads) void k_bp_update(const double* __rest
     sp = block_sum256(sp, red);
     sd = block_sum256(sd, red);
     if (tid == 0) {
-        seg_cnt[blockIdx.x] = (int)(base - j0);
-        rpart[blockIdx.x] = sp;
-        rpart[kIstaMaxSegs + blockIdx.x] = sd;
+        seg_cnt[seg] = (int)(base - j0);
+        rpart[seg] = sp;
+        rpart[kIstaMaxSegs + seg] = sd;
     }
+}
+__global__ __launch_bounds__(kIstaThreads) void k_bp_update(const double* __restrict__ c, const double* __restrict__ w, int64_t nw, double rho,
+                                                            double* __restrict__ z, double* __restrict__ u, int64_t N, int64_t seg_len,
+                                                            int* __restrict__ lidx, double* __restrict__ lval, int* __restrict__ seg_cnt,
+                                                            double* __restrict__ rpart) {
+    bp_update_body((int)blockIdx.x, c, w, nw, rho, z, u, N, seg_len, lidx, lval, seg_cnt, rpart);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The group forms of csmp_bp_batch (host/bp_batch.hpp): ONE launch does a kernel's work for every live member of a lockstep group.
+// The member is the grid's third axis; its pointers come from this kernel-argument struct (the live members in entries [0, n), in
+// slot order).  Every member's workgroups run the single kernels' bodies above (and ista_axpy_body / ista_resum_body, csmp_ista.hpp)
+// on the member's own buffers: per member the arithmetic and its order are the single solve's.  The weights are shared.
+constexpr int kBpGroupMax = 8;
+struct BpGroup {
+    int n;
+    const double* c[kBpGroupMax];                                                  // the pass's c = A'y (the member's slot)
+    double *z[kBpGroupMax], *u[kBpGroupMax];                                       // the iterates
+    int *lidx[kBpGroupMax], *seg_cnt[kBpGroupMax]; double* lval[kBpGroupMax];      // the list of z+
+    double* rpart[kBpGroupMax];                                                    // the residual norms' partials
+    double* part[kBpGroupMax]; unsigned* nnz[kBpGroupMax];                         // the axpy's partials and the list's length
+    const double* b[kBpGroupMax]; double* r[kBpGroupMax];                          // the member's slot
+    const double* g[kBpGroupMax]; double *p[kBpGroupMax], *q[kBpGroupMax], *e[kBpGroupMax];
+};
+static_assert(sizeof(BpGroup) <= 4096, "kernel arguments");
+__global__ __launch_bounds__(kIstaThreads) void k_bp_update_group(const BpGroup G, const double* __restrict__ w, int64_t nw, double rho, int64_t N,
+                                                                  int64_t seg_len) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n) return;
+    bp_update_body((int)blockIdx.x, G.c[m], w, nw, rho, G.z[m], G.u[m], N, seg_len, G.lidx[m], G.lval[m], G.seg_cnt[m], G.rpart[m]);
+}
+template <typename TA>
+__global__ __launch_bounds__(kIstaThreads) void k_ista_axpy_group(const TA* __restrict__ A, int64_t ld, int Mv, int nseg, int64_t seg_len,
+                                                                  const BpGroup G) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n) return;
+    ista_axpy_body<TA>(A, ld, Mv, G.seg_cnt[m], nseg, seg_len, G.lidx[m], G.lval[m], G.part[m], G.nnz[m]);
+}
+__global__ __launch_bounds__(kIstaThreads) void k_ista_resum_group(int Mv, int M, int P, const BpGroup G) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n) return;
+    ista_resum_body(G.part[m], Mv, M, G.nnz[m], P, G.b[m], G.r[m]);
+}
+__global__ __launch_bounds__(256) void k_bp_pq_group(int M, const BpGroup G) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n) return;
+    bp_pq_body((int)blockIdx.x, G.b[m], G.r[m], G.g[m], M, G.p[m], G.q[m], G.e[m]);
 }
 
 // res[0] = |u+ - u|^2, res[1] = |z+ - z|^2: the nseg <= 1024 partials of each, four per thread in order, then block_sum256

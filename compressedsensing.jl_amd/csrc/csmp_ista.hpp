@@ -119,11 +119,12 @@ __global__ __launch_bounds__(kIstaThreads) void k_ista_update(const double* __re
 // size, not from the list -- the workgroups beyond ista_parts(n, P) leave at once, and k_ista_resum adds that many partials.
 // Ragged columns: a lane past the column's end re-reads the column's last vector (valid memory, no predicate in the load stream)
 // and its sums are not stored; a wave wholly past the end loads nothing.
+// The body is shared with k_ista_axpy_group (csmp_bp.hpp): it reads blockIdx.x / .y and gridDim.x only.
 template <typename TA>
-__global__ __launch_bounds__(kIstaThreads) void k_ista_axpy(const TA* __restrict__ A, int64_t ld, int Mv, const int* __restrict__ seg_cnt,
-                                                            int nseg, int64_t seg_len, const int* __restrict__ lidx,
-                                                            const double* __restrict__ lval, double* __restrict__ part,
-                                                            unsigned* __restrict__ nnz_out) {
+__device__ __forceinline__ void ista_axpy_body(const TA* __restrict__ A, int64_t ld, int Mv, const int* __restrict__ seg_cnt,
+                                               int nseg, int64_t seg_len, const int* __restrict__ lidx,
+                                               const double* __restrict__ lval, double* __restrict__ part,
+                                               unsigned* __restrict__ nnz_out) {
     using VT = typename Vec<TA>::type;
     constexpr int VEC = Vec<TA>::n, L = kIstaL, NB = kIstaNB;
     __shared__ unsigned off[kIstaMaxSegs + 1];
@@ -215,11 +216,18 @@ __global__ __launch_bounds__(kIstaThreads) void k_ista_axpy(const TA* __restrict
         }
     }
 }
+template <typename TA>
+__global__ __launch_bounds__(kIstaThreads) void k_ista_axpy(const TA* __restrict__ A, int64_t ld, int Mv, const int* __restrict__ seg_cnt,
+                                                            int nseg, int64_t seg_len, const int* __restrict__ lidx,
+                                                            const double* __restrict__ lval, double* __restrict__ part,
+                                                            unsigned* __restrict__ nnz_out) {
+    ista_axpy_body<TA>(A, ld, Mv, seg_cnt, nseg, seg_len, lidx, lval, part, nnz_out);
+}
 
 // r = b - (part[0] + part[1] + ... ), the first ista_parts(n, P) partials: a workgroup takes 64 rows, its four waves a quarter
 // of the partials each (in order), and the four sums are added as (s0 + s1) + (s2 + s3).  n = 0: r = b.
-__global__ __launch_bounds__(kIstaThreads) void k_ista_resum(const double* __restrict__ part, int Mv, int M, const unsigned* __restrict__ nnz,
-                                                             int P, const double* __restrict__ b, double* __restrict__ r) {
+__device__ __forceinline__ void ista_resum_body(const double* __restrict__ part, int Mv, int M, const unsigned* __restrict__ nnz,
+                                                int P, const double* __restrict__ b, double* __restrict__ r) {
     __shared__ double red[kIstaThreads / kWave][kWave];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int Pa = ista_parts(*nnz, P);
@@ -230,6 +238,11 @@ __global__ __launch_bounds__(kIstaThreads) void k_ista_resum(const double* __res
     red[wave][lane] = s;
     __syncthreads();
     if (wave == 0 && row < M) r[row] = b[row] - ((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]));
+}
+
+__global__ __launch_bounds__(kIstaThreads) void k_ista_resum(const double* __restrict__ part, int Mv, int M, const unsigned* __restrict__ nnz,
+                                                             int P, const double* __restrict__ b, double* __restrict__ r) {
+    ista_resum_body(part, Mv, M, nnz, P, b, r);
 }
 
 }  // namespace csmp

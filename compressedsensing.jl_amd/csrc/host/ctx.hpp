@@ -178,6 +178,20 @@ struct BpBuf {
     bool notpd = false;     // ... and the factorisation met a pivot that is not positive to working precision
 };
 
+// csmp_bp_batch (host/bp_batch.hpp): what csmp_bp keeps per solve in IstaBuf and BpBuf, for each of R members of a lockstep group --
+// member m's share of an array starts m strides in: z and u (N each), the list of z+ (lidx, lval: N; seg_cnt: kIstaMaxSegs), the
+// axpy's partials (P Mv) and the list's length, the six M-vectors p, q, e, v, y, g (Mp each, zero beyond M), rpart (2 kIstaMaxSegs);
+// res (a pair per member) and nrm (||r||^2 per member) are read by the host in one piece.  b, r, c and the pass's partials are the
+// solver slots'; G and the factor are BpBuf's; the weights IstaBuf's.  Made on first use, sized by the dictionary and R: all or none.
+struct BpBatchBuf {
+    double *zu = nullptr, *lval = nullptr, *part = nullptr, *vec = nullptr, *rpart = nullptr, *res = nullptr, *nrm = nullptr;
+    int *lidx = nullptr, *seg_cnt = nullptr;
+    unsigned* nnz = nullptr;
+    int R = 0;       // members the buffers were made for (0: none)
+    int64_t N = 0;   // ... atoms
+    int Mv = 0, P = 0, Mp = 0;
+};
+
 // basis pursuit denoising (csmp_bpd.hpp, host/bpd.hpp): the augmented matrix [K | I], K = I + A A', that the blocked Cholesky turns into R
 // beside R^-T (BpBuf's layout; R^-1 in its rows from np on) -- A A' itself is a temporary of the factorisation -- the verdict, the
 // M-vectors of the iteration and the partial sums, made on first use, sized by the dictionary: all of them, or none.  Apart from BpBuf:
@@ -331,6 +345,7 @@ struct csmp_ctx {
     AnalysisBuf analysis;
     RwBuf rw;
     BpBuf bp;
+    BpBatchBuf bpb;
     BpdBuf bpd;
     SblBuf sbl;
     FsblBuf fsbl;

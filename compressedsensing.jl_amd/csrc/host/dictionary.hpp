@@ -248,6 +248,7 @@ static int dict_forget(csmp_ctx* ctx) {
     analysis_free(ctx->analysis);
     rw_free(ctx->rw);
     bp_free(ctx->bp);
+    bpb_free(ctx->bpb);
     bpd_free(ctx->bpd);
     sbl_free(ctx->sbl);
     fsbl_free(ctx->fsbl);

@@ -107,6 +107,11 @@ static void bp_free(BpBuf& t) {
     t = BpBuf();
 }
 
+static void bpb_free(BpBatchBuf& t) {
+    dfree(t.zu); dfree(t.lval); dfree(t.part); dfree(t.vec); dfree(t.rpart); dfree(t.res); dfree(t.nrm); dfree(t.lidx); dfree(t.seg_cnt); dfree(t.nnz);
+    t = BpBatchBuf();
+}
+
 static void bpd_free(BpdBuf& t) {
     dfree(t.Gm); dfree(t.pivref); dfree(t.Dfac); dfree(t.vec); dfree(t.rpart); dfree(t.mpart); dfree(t.res); dfree(t.st);
     t = BpdBuf();
@@ -149,6 +154,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     analysis_free(ctx->analysis);
     rw_free(ctx->rw);
     bp_free(ctx->bp);
+    bpb_free(ctx->bpb);
     bpd_free(ctx->bpd);
     sbl_free(ctx->sbl);
     fsbl_free(ctx->fsbl);

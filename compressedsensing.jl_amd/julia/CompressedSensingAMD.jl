@@ -248,6 +248,28 @@ bp(A::MatOrDict, b::AbstractVector; rho::Real = 1.0, maxiter::Int = 16384, tol::
 bp(A::MatOrDict, b::AbstractVector, w::AbstractVector; rho::Real = 1.0, maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32,
    return_info::Bool = false) = bp_call(A, b, convert(Vector{Float64}, w), rho, maxiter, tol, check_every, return_info)
 const basispursuit = bp
+# [bp(A, B[:, s], w) for s in axes(B, 2)]: up to eight signals take their iterations in lockstep on shared launches, every result bp's bit
+# for bit (csmp_bp_batch).  The weights are shared by all signals.
+function bp_batch_call(A::MatOrDict, B::AbstractMatrix, w::Vector{Float64}, rho::Real, maxiter::Int, tol::Real, check_every::Int, return_info::Bool)
+    D = dict(A)
+    BB = B isa StridedMatrix && eltype(B) <: Union{Float32,Float64} && stride(B, 1) == 1 ? B : convert(Matrix{Float64}, B)
+    size(BB, 1) == size(D, 1) || throw(DimensionMismatch("size(B, 1) = $(size(BB, 1)) but size(A, 1) = $(size(D, 1))"))
+    nsig, N = size(BB, 2), size(D, 2)
+    X = zeros(Float64, N, nsig)
+    it, rn, flags = zeros(Int64, nsig), zeros(Float64, nsig), zeros(Cint, nsig)
+    GC.@preserve BB w X it rn flags check(D, ccall((:csmp_bp_batch, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Ptr{Cdouble}, Int64, Cdouble, Int64, Cdouble, Int64, Ptr{Cdouble}, Int64, Cint,
+         Ptr{Int64}, Ptr{Cdouble}, Ptr{Cint}),
+        D.ctx, BB, dtype_code(eltype(BB)), max(stride(BB, 2), size(BB, 1)), nsig, CSMP_HOST, w, length(w), rho, maxiter, tol, check_every, X, max(N, 1),
+        CSMP_HOST, it, rn, flags))
+    xs = [sparse(X[:, s]) for s in 1:nsig]
+    info = (iterations = it, converged = flags .& CSMP_BP_CONVERGED .!= 0, resnorm = rn, factored = nsig > 0 && flags[1] & CSMP_BP_FACTORED != 0)
+    return return_info ? (xs, info) : xs
+end
+bp_batch(A::MatOrDict, B::AbstractMatrix; rho::Real = 1.0, maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32, return_info::Bool = false) =
+    bp_batch_call(A, B, Float64[1.0], rho, maxiter, tol, check_every, return_info)
+bp_batch(A::MatOrDict, B::AbstractMatrix, w::AbstractVector; rho::Real = 1.0, maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32,
+         return_info::Bool = false) = bp_batch_call(A, B, convert(Vector{Float64}, w), rho, maxiter, tol, check_every, return_info)
 function bp_reweighted(A::MatOrDict, b::AbstractVector, scheme::Integer, ε::Real, ard_iter::Int, maxiter::Int, min_decrease::Real, rho::Real,
                        inner_maxiter::Int, tol::Real, check_every::Int, return_weights::Bool)
     D = dict(A)

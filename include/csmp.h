@@ -456,6 +456,31 @@ int csmp_bp(csmp_ctx *ctx, const void *b, int b_dtype, const double *w, int64_t 
             double rho, int64_t maxiter, double tol, int64_t check_every,
             double *x, int x_loc, int64_t *iterations, double *resnorm, int *flags);
 
+/* bp_batch: csmp_bp for every column of B, the signals in lockstep on shared launches.  Everything an iteration of csmp_bp reads in
+ * bulk -- the dictionary, R^-1, R^-T, G -- is the same for every signal: a group of up to eight signals (the groups of csmp_mp_batch:
+ * csmp_tune group_max / group_wide apply) takes its iterations together, eight launches a step however many are live -- three M x M
+ * products with one read of each matrix for all right-hand sides, one shared pass over A, one launch each for the update, the
+ * residual's two steps and the M-vector step.  Solves end at different iterations: a finished signal's slot is refilled with the next
+ * column at the following multiple of check_every.
+ * Contract: column s of X, iterations[s], resnorm[s] and the CSMP_BP_CONVERGED bit of flags[s] are those of
+ * csmp_bp(ctx, B[:, s], ...) with the same w, rho, maxiter, tol, check_every, BIT FOR BIT, whatever nsig and the group sizes are.
+ * CSMP_BP_FACTORED is set in flags[0] only, and only when this call formed the factor (what a loop over csmp_bp would report).
+ * B: size(A,1) x nsig, column-major, leading dimension ldB >= size(A,1), CSMP_F32 or CSMP_F64, on the host or the device (b_loc).
+ * X: size(A,2) x nsig doubles, leading dimension ldX >= size(A,2), on the host or the device (x_loc); column s receives the exactly
+ * sparse z of signal s, rows beyond size(A,2) are not touched.  w, nw: csmp_bp's, a host array, shared by all signals.  iterations,
+ * resnorm, flags: host arrays of nsig entries, each may be NULL.  maxiter = 0: every column zero, iterations 0, resnorm ||b||.
+ * A dictionary without a shared pass (csmp_sweep_config: group 0), CSMP_OPT_SCREENED_SWEEP switched on and nsig = 1 take csmp_bp's
+ * own solve signal by signal: the same outputs.
+ * Memory beside csmp_bp's, kept by the context until csmp_set_dictionary: per member of a group 2 size(A,2) + the list (1.5 size(A,2))
+ * doubles and the residual's partials -- 8 MiB + 128 MiB for eight members at 4096 x 65536.
+ * CSMP_EDIM: ldB < size(A,1), ldX < size(A,2), a w of another length, size(A,1) > size(A,2).  CSMP_EINVAL: nsig < 0, null pointers, a
+ * dtype / location that is neither, csmp_bp's knobs and weights, A A' not positive definite.  nsig = 0: CSMP_OK, nothing is touched.
+ * CSMP_ERANGE, CSMP_ESTATE: csmp_bp's.  CSMP_ENOMEM: a buffer could not be allocated; no partial buffers are left behind and the
+ * context stays usable. */
+int csmp_bp_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc,
+                  const double *w, int64_t nw, double rho, int64_t maxiter, double tol, int64_t check_every,
+                  double *X, int64_t ldX, int x_loc, int64_t *iterations, double *resnorm, int *flags);
+
 /* bp_candes / bp_ard: basispursuit_reweighting (:18-31) with csmp_bp's solve:  x = solve(w = 1);  then for i = 2 .. outer_maxiter:  w from x
  * (scheme, eps, ard_iter: as csmp_ista_reweighted; CSMP_REWEIGHT_ARD takes supports of up to min(size(A,1), CSMP_ARD_KMAX) atoms);
  * xs = solve(w), WARM-STARTED from the z, u, p, q of the previous solve;  norm(xs - x) < min_decrease: return xs;  else x = xs.
