@@ -93,6 +93,8 @@ SIGNATURES = {
                                      C.POINTER(i64), C.POINTER(C.c_double)]),
     "csmp_bpd": (C.c_int, [vp, vp, C.c_int, C.c_double, vp, i64, C.c_double, i64, C.c_double, i64, vp, C.c_int, C.POINTER(i64), C.POINTER(C.c_double),
                            C.POINTER(C.c_int)]),
+    "csmp_bpd_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, vp, i64, vp, i64, C.c_double, i64, C.c_double, i64, vp, i64, C.c_int,
+                                 C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "csmp_bpd_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, i64, i64, C.c_double, C.c_double, i64, C.c_double, i64, vp, C.c_int,
                                       vp, C.POINTER(i64), C.POINTER(C.c_double)]),
     "csmp_sbl": (C.c_int, [vp, vp, C.c_int, C.c_double, i64, C.c_double, vp, vp, vp, C.c_int, C.POINTER(i64), C.POINTER(C.c_int)]),
@@ -898,6 +900,51 @@ class Context:
         self.call("csmp_bpd", vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64, C.c_double(delta), ptr(w), i64(len(w)), C.c_double(rho),
                   i64(int(maxiter)), C.c_double(tol), i64(int(check_every)), vp(x.data_ptr()), DEVICE, C.byref(it), C.byref(rn), C.byref(flags))
         return self._bpd_info(it, rn, flags)
+
+    def _bpd_batch_call(self, B, code, ldB, nsig, b_loc, delta, w, X, ldX, x_loc, rho, maxiter, tol, check_every):
+        w, _, _ = self._ista_args(w, None, None)
+        delta = np.ascontiguousarray(np.atleast_1d(np.asarray(delta, dtype=np.float64)))
+        if delta.ndim != 1 or len(delta) not in (1, nsig):
+            raise CsmpError(EDIM, f"length(delta) = {delta.shape} but B has {nsig} columns: one radius, or one per signal")
+        it, rn, flags = np.zeros(max(nsig, 1), np.int64), np.zeros(max(nsig, 1), np.float64), np.zeros(max(nsig, 1), np.int32)
+        self.call("csmp_bpd_batch", B, code, i64(ldB), i64(nsig), b_loc, ptr(delta), i64(len(delta)), ptr(w), i64(len(w)), C.c_double(rho),
+                  i64(int(maxiter)), C.c_double(tol), i64(int(check_every)), X, i64(ldX), x_loc, it.ctypes.data_as(C.POINTER(i64)),
+                  rn.ctypes.data_as(C.POINTER(C.c_double)), flags.ctypes.data_as(C.POINTER(C.c_int)))
+        it, rn, flags = it[:nsig], rn[:nsig], flags[:nsig]
+        return {"iterations": it, "converged": (flags & BPD_CONVERGED) != 0, "resnorm": rn, "factored": bool(nsig > 0 and flags[0] & BPD_FACTORED)}
+
+    def bpd_batch(self, B, delta, w=1.0, rho=BPD_RHO, maxiter=16384, tol=1e-8, check_every=32):
+        """csmp_bpd_batch on the host matrix B (M x nsig): bpd for every column, the signals of a group in lockstep on shared launches --
+        (X, Float64 N x nsig in Fortran order; info = iterations int64[nsig], converged bool[nsig], resnorm float64[nsig], factored).
+        Column s and its info are bpd(B[:, s], delta[s], ...)'s bit for bit.  delta: one radius or nsig of them; w: one weight or N of
+        them, shared by all signals."""
+        B = np.asfortranarray(B)
+        if B.dtype not in (np.float32, np.float64):
+            B = B.astype(np.float64)
+        if B.ndim != 2 or B.shape[0] != self.M:
+            raise CsmpError(EDIM, f"size(B) = {B.shape} but size(A, 1) = {self.M}")
+        nsig = B.shape[1]
+        X = np.zeros((max(self.N, 1), nsig), np.float64, order="F")
+        info = self._bpd_batch_call(ptr(B), dtype_code(B.dtype), max(self.M, 1), nsig, HOST, delta, w, ptr(X), max(self.N, 1), HOST, rho, maxiter,
+                                    tol, check_every)
+        return X[:self.N], info
+
+    def bpd_batch_device(self, B, delta, w, X, rho=BPD_RHO, maxiter=16384, tol=1e-8, check_every=32):
+        """torch CUDA tensors whose COLUMNS are the signals and the results, as bp_batch_device's: B (M, nsig) float32 / float64 with
+        stride (1, ldB >= M), X (N, nsig) float64 with stride (1, ldX >= N).  delta: host values, one or nsig.  Returns info; the work
+        is done when the call returns."""
+        import torch
+        if not (B.is_cuda and B.dim() == 2 and B.shape[0] == self.M and B.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "B must be a CUDA matrix of size(A, 1) rows, float32 or float64")
+        nsig = B.shape[1]
+        if not (X.is_cuda and X.dim() == 2 and X.shape == (self.N, nsig) and X.dtype == torch.float64):
+            raise CsmpError(EDIM, "X must be a CUDA float64 matrix of size(A, 2) rows and B's columns")
+        ldB = B.stride(1) if nsig > 1 else max(self.M, 1)
+        ldX = X.stride(1) if nsig > 1 else max(self.N, 1)
+        if (self.M > 1 and B.stride(0) != 1) or (self.N > 1 and X.stride(0) != 1) or ldB < self.M or ldX < self.N:
+            raise CsmpError(EDIM, "B and X must be column-major: unit row stride, column strides of at least their row counts")
+        return self._bpd_batch_call(vp(B.data_ptr()), F32 if B.dtype == torch.float32 else F64, ldB, nsig, DEVICE, delta, w, vp(X.data_ptr()), ldX,
+                                    DEVICE, rho, maxiter, tol, check_every)
 
     def bpd_reweighted(self, b, delta, scheme, eps=None, ard_iter=8, outer_maxiter=8, min_decrease=1e-4, rho=BPD_RHO, maxiter=16384, tol=1e-8,
                        check_every=32, return_weights=False):

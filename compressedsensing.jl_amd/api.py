@@ -432,6 +432,40 @@ def bpd(A, b, delta, w=None, *, rho=BPD_RHO, maxiter=16384, tol=1e-8, check_ever
 basis_pursuit_denoising = bpd
 
 
+def bpd_batch(A, B, delta, w=None, *, rho=BPD_RHO, maxiter=16384, tol=1e-8, check_every=32, return_info=False):
+    """[bpd(A, B[:, s], δ[s], w) for s in axes(B, 2)] on one GPU: up to eight signals take their ADMM iterations in lockstep, so the
+    dictionary and the two triangular factors of I + A Aᵀ are read once per step for all of them; a finished signal's place is taken by the
+    next column.  Every result is bpd's bit for bit.  δ: a scalar, or a 1-D array with one radius per column of B; the weights are shared
+    by all signals.  Returns a list of SparseVectors; return_info=True: (list, info) with info = {iterations int64[nsig], converged
+    bool[nsig], resnorm float64[nsig], factored}."""
+    M, N = _bpd_knobs(A, 0.0, rho, maxiter, tol, check_every)
+    w = np.ones(1) if w is None else np.atleast_1d(np.asarray(w, dtype=np.float64))
+    if w.ndim != 1 or len(w) not in (1, N):
+        raise ValueError(f"length(w) = {w.shape} but size(A, 2) = {N}")
+    if not np.all((w >= 0) & np.isfinite(w)):
+        raise ValueError("the weights have to be non-negative and finite")
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] != M:
+        raise ValueError(f"size(B) = {B.shape} but size(A, 1) = {M}: B holds one signal per column")
+    delta = np.asarray(delta, dtype=np.float64)
+    if delta.ndim > 1 or (delta.ndim == 1 and len(delta) != B.shape[1]):
+        raise ValueError(f"size(delta) = {delta.shape} but B has {B.shape[1]} columns: a scalar, or one radius per signal")
+    delta = np.atleast_1d(delta)
+    if not np.all((delta >= 0) & np.isfinite(delta)):
+        raise ValueError("every delta has to be non-negative and finite")
+    D, tmp = _dict(A)
+    try:
+        X, info = D.ctx.bpd_batch(B, delta, w, float(rho), int(maxiter), float(tol), int(check_every))
+        xs = []
+        for s in range(X.shape[1]):
+            nz = np.flatnonzero(X[:, s])
+            xs.append(SparseVector(N, nz, X[nz, s]))
+        return (xs, info) if return_info else xs
+    finally:
+        if tmp:
+            D.close()
+
+
 def _bpd_reweighted(A, b, delta, scheme, eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights, ard_iter=8):
     M, N = _bpd_knobs(A, delta, rho, inner_maxiter, tol, check_every)
     if not (eps > 0 and np.isfinite(eps)):

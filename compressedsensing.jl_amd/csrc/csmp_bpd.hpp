@@ -13,6 +13,7 @@
 //   k_bpd_ball         every workgroup adds the partials of |h|^2 in index order (the same bits in each), then v+, lam+, the next en, and
 //                      one partial each of |lam+ - lam|^2 and |v+ - v|^2
 //   k_bpd_fold         the four sums of the stopping test, partials added in index order
+//   k_bpd_pq_group, k_bpd_ball_group   the two M-vector kernels for every live member of csmp_bpd_batch's group in one launch each
 //
 // Determinism: no atomics, no workgroup waits for another, every sum has a fixed order: the same bits on every run.
 #pragma once
@@ -53,12 +54,12 @@ __global__ __launch_bounds__(256) void k_bpd_start(int M, double* __restrict__ p
 }
 
 // p+ = b - r;  q+ = p + (e - y) - p+ = p - (en - yn) - p+;  h = v - y - b = v + yn - b;  hpart[workgroup] = its share of |h|^2 (thread
-// squares in index order through block_sum256; rows beyond M add zeros)
-__global__ __launch_bounds__(256) void k_bpd_pq(const double* __restrict__ b, const double* __restrict__ r, const double* __restrict__ en,
-                                                const double* __restrict__ yn, const double* __restrict__ v, int M, double* __restrict__ p,
-                                                double* __restrict__ q, double* __restrict__ h, double* __restrict__ hpart) {
+// squares in index order through block_sum256; rows beyond M add zeros).  blk: the workgroup's 256 rows.
+__device__ __forceinline__ void bpd_pq_body(const int blk, const double* __restrict__ b, const double* __restrict__ r, const double* __restrict__ en,
+                                            const double* __restrict__ yn, const double* __restrict__ v, int M, double* __restrict__ p,
+                                            double* __restrict__ q, double* __restrict__ h, double* __restrict__ hpart) {
     __shared__ double red[4];
-    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int i = blk * 256 + threadIdx.x;
     double hh = 0.0;
     if (i < M) {
         const double pn = b[i] - r[i];
@@ -68,17 +69,22 @@ __global__ __launch_bounds__(256) void k_bpd_pq(const double* __restrict__ b, co
         h[i] = hh;
     }
     const double s = block_sum256(hh * hh, red);
-    if (threadIdx.x == 0) hpart[blockIdx.x] = s;
+    if (threadIdx.x == 0) hpart[blk] = s;
+}
+__global__ __launch_bounds__(256) void k_bpd_pq(const double* __restrict__ b, const double* __restrict__ r, const double* __restrict__ en,
+                                                const double* __restrict__ yn, const double* __restrict__ v, int M, double* __restrict__ p,
+                                                double* __restrict__ q, double* __restrict__ h, double* __restrict__ hpart) {
+    bpd_pq_body((int)blockIdx.x, b, r, en, yn, v, M, p, q, h, hpart);
 }
 
 // |h|^2 = the nparts <= kBpdMaxParts partials, eight per thread in index order, then block_sum256 -- the same operations in every
 // workgroup, so every workgroup scales by the same bits.  v+ = b + h delta / |h| where |h| > delta, else b + h (h = 0 and delta = 0
 // included);  lam+ = v + yn - v+;  the next iteration's  en = -(v+ - lam+ - p+ + q+).  mpart[workgroup] = its share of |lam+ - lam|^2,
 // mpart[kBpdMaxParts + workgroup] of |v+ - v|^2.
-__global__ __launch_bounds__(256) void k_bpd_ball(const double* __restrict__ b, const double* __restrict__ h, const double* __restrict__ yn,
-                                                  const double* __restrict__ p, const double* __restrict__ q, const double* __restrict__ hpart,
-                                                  int nparts, double delta, int M, double* __restrict__ v, double* __restrict__ lam,
-                                                  double* __restrict__ en, double* __restrict__ mpart) {
+__device__ __forceinline__ void bpd_ball_body(const int blk, const double* __restrict__ b, const double* __restrict__ h, const double* __restrict__ yn,
+                                              const double* __restrict__ p, const double* __restrict__ q, const double* __restrict__ hpart,
+                                              int nparts, double delta, int M, double* __restrict__ v, double* __restrict__ lam,
+                                              double* __restrict__ en, double* __restrict__ mpart) {
     __shared__ double red[4];
     double a = 0.0;
 #pragma unroll
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(256) void k_bpd_ball(const double* __restrict__ b, 
     }
     const double nh = sqrt(block_sum256(a, red));
     const double scale = nh > delta ? delta / nh : 1.0;
-    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int i = blk * 256 + threadIdx.x;
     double dl = 0.0, dv = 0.0;
     if (i < M) {
         const double vo = v[i], lo = lam[i];
@@ -103,9 +109,40 @@ __global__ __launch_bounds__(256) void k_bpd_ball(const double* __restrict__ b, 
     dl = block_sum256(dl * dl, red);
     dv = block_sum256(dv * dv, red);
     if (threadIdx.x == 0) {
-        mpart[blockIdx.x] = dl;
-        mpart[kBpdMaxParts + blockIdx.x] = dv;
+        mpart[blk] = dl;
+        mpart[kBpdMaxParts + blk] = dv;
     }
+}
+__global__ __launch_bounds__(256) void k_bpd_ball(const double* __restrict__ b, const double* __restrict__ h, const double* __restrict__ yn,
+                                                  const double* __restrict__ p, const double* __restrict__ q, const double* __restrict__ hpart,
+                                                  int nparts, double delta, int M, double* __restrict__ v, double* __restrict__ lam,
+                                                  double* __restrict__ en, double* __restrict__ mpart) {
+    bpd_ball_body((int)blockIdx.x, b, h, yn, p, q, hpart, nparts, delta, M, v, lam, en, mpart);
+}
+
+// The group forms of csmp_bpd_batch (host/bpd_batch.hpp), as csmp_bp.hpp's: the member is the grid's third axis, its pointers and its
+// ball's radius come from this kernel-argument struct (the live members in entries [0, n), in slot order), its workgroups run the
+// single kernels' bodies on the member's own buffers -- per member the arithmetic and the order of every sum are the single solve's.
+// k_bpd_ball_group's workgroups read their OWN member's hpart only, written by the launch before: nobody waits, no atomics.
+struct BpdGroup {
+    int n;
+    const double *b[kBpGroupMax], *r[kBpGroupMax];                                 // the member's slot
+    double *p[kBpGroupMax], *q[kBpGroupMax], *en[kBpGroupMax], *v[kBpGroupMax], *lam[kBpGroupMax], *h[kBpGroupMax];
+    const double* yn[kBpGroupMax];
+    double* mpart[kBpGroupMax];                                                    // |lam+ - lam|^2, |v+ - v|^2, |h|^2: kBpdMaxParts each
+    double delta[kBpGroupMax];                                                     // the radius of the member's ball
+};
+static_assert(sizeof(BpdGroup) <= 4096, "kernel arguments");
+__global__ __launch_bounds__(256) void k_bpd_pq_group(int M, const BpdGroup G) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n) return;
+    bpd_pq_body((int)blockIdx.x, G.b[m], G.r[m], G.en[m], G.yn[m], G.v[m], M, G.p[m], G.q[m], G.h[m], G.mpart[m] + 2 * kBpdMaxParts);
+}
+__global__ __launch_bounds__(256) void k_bpd_ball_group(int M, int nparts, const BpdGroup G) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n) return;
+    bpd_ball_body((int)blockIdx.x, G.b[m], G.h[m], G.yn[m], G.p[m], G.q[m], G.mpart[m] + 2 * kBpdMaxParts, nparts, G.delta[m], M, G.v[m], G.lam[m],
+                  G.en[m], G.mpart[m]);
 }
 
 // res[0] = |u+ - u|^2, res[1] = |z+ - z|^2 (k_bp_update's partials, k_bp_fold's order), res[2] = |lam+ - lam|^2, res[3] = |v+ - v|^2

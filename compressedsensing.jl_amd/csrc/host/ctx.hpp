@@ -205,6 +205,21 @@ struct BpdBuf {
     bool notpd = false;     // ... and the factorisation met a pivot that is not positive (K is positive definite: a fault, not a verdict on A)
 };
 
+// csmp_bpd_batch (host/bpd_batch.hpp): what csmp_bpd keeps per solve in IstaBuf and BpdBuf, for each of R members of a lockstep group,
+// in BpBatchBuf's layout -- member m's share of an array starts m strides in: z and u (N each), the list of z+ (lidx, lval: N; seg_cnt:
+// kIstaMaxSegs), the axpy's partials (P Mv) and the list's length, the eight M-vectors p, q, en, tmp, yn, v, lam, h (Mp each, zero
+// beyond M), rpart (2 kIstaMaxSegs), mpart (3 kBpdMaxParts); res (a quadruple per member) and nrm (||r||^2 per member) are read by
+// the host in one piece.  b, r, c and the pass's partials are the solver slots'; the factor is BpdBuf's; the weights IstaBuf's.
+// Made on first use, sized by the dictionary and R: all or none.
+struct BpdBatchBuf {
+    double *zu = nullptr, *lval = nullptr, *part = nullptr, *vec = nullptr, *rpart = nullptr, *mpart = nullptr, *res = nullptr, *nrm = nullptr;
+    int *lidx = nullptr, *seg_cnt = nullptr;
+    unsigned* nnz = nullptr;
+    int R = 0;       // members the buffers were made for (0: none)
+    int64_t N = 0;   // ... atoms
+    int Mv = 0, P = 0, Mp = 0;
+};
+
 // sparse Bayesian learning (csmp_sbl.hpp, host/sbl.hpp): k_rowgram's partials of A Gamma A' and their sum G (M x M), the augmented
 // matrix [C | I], C = sigma2 I + G, that the blocked Cholesky turns into R beside R^-T (BpBuf's layout; R^-1 = L^-T in its rows from np
 // on), the M-vectors b and t = L^-1 b, the N-vectors gam, s, q and x, the partials and the verdicts, made on first use, sized by the
@@ -347,6 +362,7 @@ struct csmp_ctx {
     BpBuf bp;
     BpBatchBuf bpb;
     BpdBuf bpd;
+    BpdBatchBuf bpdb;
     SblBuf sbl;
     FsblBuf fsbl;
     // profiling

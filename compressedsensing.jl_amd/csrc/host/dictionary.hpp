@@ -250,6 +250,7 @@ static int dict_forget(csmp_ctx* ctx) {
     bp_free(ctx->bp);
     bpb_free(ctx->bpb);
     bpd_free(ctx->bpd);
+    bpdb_free(ctx->bpdb);
     sbl_free(ctx->sbl);
     fsbl_free(ctx->fsbl);
     return CSMP_OK;

@@ -117,6 +117,12 @@ static void bpd_free(BpdBuf& t) {
     t = BpdBuf();
 }
 
+static void bpdb_free(BpdBatchBuf& t) {
+    dfree(t.zu); dfree(t.lval); dfree(t.part); dfree(t.vec); dfree(t.rpart); dfree(t.mpart); dfree(t.res); dfree(t.nrm); dfree(t.lidx);
+    dfree(t.seg_cnt); dfree(t.nnz);
+    t = BpdBatchBuf();
+}
+
 static void sbl_free(SblBuf& t) {
     dfree(t.Gpart); dfree(t.G); dfree(t.Gm); dfree(t.pivref); dfree(t.Dfac); dfree(t.vec); dfree(t.gam); dfree(t.s); dfree(t.q); dfree(t.x);
     dfree(t.part); dfree(t.info); dfree(t.st);
@@ -156,6 +162,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     bp_free(ctx->bp);
     bpb_free(ctx->bpb);
     bpd_free(ctx->bpd);
+    bpdb_free(ctx->bpdb);
     sbl_free(ctx->sbl);
     fsbl_free(ctx->fsbl);
     if (ctx->comm) (void)csmp_comm_free(ctx);

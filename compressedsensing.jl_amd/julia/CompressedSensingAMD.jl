@@ -312,6 +312,32 @@ bpd(A::MatOrDict, b::AbstractVector, δ::Real; rho::Real = 100.0, maxiter::Int =
 bpd(A::MatOrDict, b::AbstractVector, δ::Real, w::AbstractVector; rho::Real = 100.0, maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32,
     return_info::Bool = false) = bpd_call(A, b, δ, convert(Vector{Float64}, w), rho, maxiter, tol, check_every, return_info)
 const basis_pursuit_denoising = bpd
+# [bpd(A, B[:, s], δ[s], w) for s in axes(B, 2)]: up to eight signals take their iterations in lockstep on shared launches, every result
+# bpd's bit for bit (csmp_bpd_batch).  δ: one radius, or one per column of B.  The weights are shared by all signals.
+function bpd_batch_call(A::MatOrDict, B::AbstractMatrix, δ::Union{Real,AbstractVector}, w::Vector{Float64}, rho::Real, maxiter::Int, tol::Real,
+                        check_every::Int, return_info::Bool)
+    D = dict(A)
+    BB = B isa StridedMatrix && eltype(B) <: Union{Float32,Float64} && stride(B, 1) == 1 ? B : convert(Matrix{Float64}, B)
+    size(BB, 1) == size(D, 1) || throw(DimensionMismatch("size(B, 1) = $(size(BB, 1)) but size(A, 1) = $(size(D, 1))"))
+    nsig, N = size(BB, 2), size(D, 2)
+    dd = δ isa Real ? Float64[δ] : convert(Vector{Float64}, δ)
+    δ isa Real || length(dd) == nsig || throw(DimensionMismatch("length(δ) = $(length(dd)) but size(B, 2) = $nsig"))
+    X = zeros(Float64, N, nsig)
+    it, rn, flags = zeros(Int64, nsig), zeros(Float64, nsig), zeros(Cint, nsig)
+    GC.@preserve BB dd w X it rn flags check(D, ccall((:csmp_bpd_batch, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Cdouble, Int64, Cdouble, Int64, Ptr{Cdouble}, Int64,
+         Cint, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cint}),
+        D.ctx, BB, dtype_code(eltype(BB)), max(stride(BB, 2), size(BB, 1)), nsig, CSMP_HOST, dd, length(dd), w, length(w), rho, maxiter, tol, check_every,
+        X, max(N, 1), CSMP_HOST, it, rn, flags))
+    xs = [sparse(X[:, s]) for s in 1:nsig]
+    info = (iterations = it, converged = flags .& CSMP_BPD_CONVERGED .!= 0, resnorm = rn, factored = nsig > 0 && flags[1] & CSMP_BPD_FACTORED != 0)
+    return return_info ? (xs, info) : xs
+end
+bpd_batch(A::MatOrDict, B::AbstractMatrix, δ::Union{Real,AbstractVector}; rho::Real = 100.0, maxiter::Int = 16384, tol::Real = 1e-8,
+          check_every::Int = 32, return_info::Bool = false) = bpd_batch_call(A, B, δ, Float64[1.0], rho, maxiter, tol, check_every, return_info)
+bpd_batch(A::MatOrDict, B::AbstractMatrix, δ::Union{Real,AbstractVector}, w::AbstractVector; rho::Real = 100.0, maxiter::Int = 16384,
+          tol::Real = 1e-8, check_every::Int = 32, return_info::Bool = false) =
+    bpd_batch_call(A, B, δ, convert(Vector{Float64}, w), rho, maxiter, tol, check_every, return_info)
 function bpd_reweighted(A::MatOrDict, b::AbstractVector, δ::Real, scheme::Integer, ε::Real, ard_iter::Int, maxiter::Int, min_decrease::Real,
                         rho::Real, inner_maxiter::Int, tol::Real, check_every::Int, return_weights::Bool)
     D = dict(A)

@@ -524,6 +524,37 @@ int csmp_bpd(csmp_ctx *ctx, const void *b, int b_dtype, double delta, const doub
              double rho, int64_t maxiter, double tol, int64_t check_every,
              double *x, int x_loc, int64_t *iterations, double *resnorm, int *flags);
 
+/* bpd_batch: csmp_bpd for every column of B, the signals in lockstep on shared launches -- csmp_bp_batch's scheme for data that carry
+ * noise.  Everything an iteration of csmp_bpd reads in bulk -- the dictionary, R^-1, R^-T of K = I + A A' -- is the same for every
+ * signal: a group of up to eight signals (the groups of csmp_mp_batch: csmp_tune group_max / group_wide apply) takes its iterations
+ * together, eight launches a step however many are live -- two triangular M x M products with one read of each triangle for all
+ * right-hand sides, one shared pass over A, one launch each for the update, the residual's two steps and the two steps of the
+ * M-vector stage (the projection on every member's own ball).  Solves end at different iterations: a finished signal's slot is
+ * refilled with the next column at the following multiple of check_every.
+ * Contract: column s of X, iterations[s], resnorm[s] and the CSMP_BPD_CONVERGED bit of flags[s] are those of
+ * csmp_bpd(ctx, B[:, s], delta[s], ...) with the same w, rho, maxiter, tol, check_every, BIT FOR BIT, whatever nsig and the group
+ * sizes are.  CSMP_BPD_FACTORED is set in flags[0] only, and only when this call formed the factor (what a loop over csmp_bpd would
+ * report).  No flag is added to csmp_bpd's two.
+ * delta, ndelta: a host array; ndelta = 1 is one radius for every signal, ndelta = nsig one radius per signal (noise levels differ
+ * from measurement to measurement); anything else: CSMP_EDIM.  Every delta is non-negative and finite.
+ * B: size(A,1) x nsig, column-major, leading dimension ldB >= size(A,1), CSMP_F32 or CSMP_F64, on the host or the device (b_loc).
+ * X: size(A,2) x nsig doubles, leading dimension ldX >= size(A,2), on the host or the device (x_loc); column s receives the exactly
+ * sparse z of signal s, rows beyond size(A,2) are not touched.  w, nw: csmp_bpd's, a host array, shared by all signals.  iterations,
+ * resnorm, flags: host arrays of nsig entries, each may be NULL.  maxiter = 0: every column zero, iterations 0, resnorm ||b||.
+ * A dictionary without a shared pass (csmp_sweep_config: group 0), CSMP_OPT_SCREENED_SWEEP switched on and nsig = 1 take csmp_bpd's
+ * own solve signal by signal: the same outputs.  size(A,1) > size(A,2) and rank-deficient dictionaries are served, as csmp_bpd
+ * serves them.
+ * Memory beside csmp_bpd's, kept by the context until csmp_set_dictionary: per member of a group 2 size(A,2) + the list
+ * (1.5 size(A,2)) doubles, the residual's partials and eight M-vectors -- 8 MiB + 128 MiB for eight members at 4096 x 65536.
+ * CSMP_EDIM: ldB < size(A,1), ldX < size(A,2), a w or a delta of another length.  CSMP_EINVAL: nsig < 0, null pointers, a dtype /
+ * location that is neither, a negative or non-finite delta, csmp_bpd's knobs and weights.  nsig = 0: CSMP_OK, nothing is touched.
+ * CSMP_ERANGE, CSMP_ESTATE: csmp_bpd's.  CSMP_ENOMEM: a buffer could not be allocated; no partial buffers are left behind and the
+ * context stays usable.  A refused call writes nothing to X, iterations, resnorm or flags. */
+int csmp_bpd_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc,
+                   const double *delta, int64_t ndelta, const double *w, int64_t nw, double rho,
+                   int64_t maxiter, double tol, int64_t check_every, double *X, int64_t ldX, int x_loc,
+                   int64_t *iterations, double *resnorm, int *flags);
+
 /* bpd_candes / bpd_ard: bpd_reweighting (:102-124) with csmp_bpd's solve:  x = solve(w = 1);  then for i = 2 .. outer_maxiter:  w from x
  * (scheme, eps, ard_iter: as csmp_ista_reweighted; CSMP_REWEIGHT_ARD takes supports of up to min(size(A,1), CSMP_ARD_KMAX) atoms);
  * xs = solve(w), WARM-STARTED from the z, u, p, q, v, lam of the previous solve;  norm(xs - x) < min_decrease: return xs;  else x = xs.
