@@ -82,6 +82,8 @@ SIGNATURES = {
     "csmp_solver_remove": (C.c_int, [vp, i64]),
     "csmp_solver_state": (C.c_int, [vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_double), vp, C.POINTER(C.c_int)]),
     "csmp_ista": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, i64, i64, C.c_double, C.c_int, vp, C.c_int, C.POINTER(C.c_double)]),
+    "csmp_ista_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, vp, i64, C.c_int,
+                                  C.POINTER(C.c_double)]),
     "csmp_ard_weights": (C.c_int, [vp, vp, vp, C.c_double, i64, vp, C.c_int]),
     "csmp_ista_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, i64, i64, C.c_double, i64, C.c_double, C.c_int, vp, C.c_int, vp,
                                        C.POINTER(i64), C.POINTER(C.c_double)]),
@@ -226,6 +228,22 @@ def dtype_code(dt):
 
 def _scheme(scheme):
     return {"candes": REWEIGHT_CANDES, "ard": REWEIGHT_ARD}.get(scheme, scheme)
+
+
+def ista_batch_weights(w, N, nsig):
+    """The weights of an ista batch as csmp_ista_batch takes them: (Float64 array in Fortran order, nw, ldw).  A scalar and an
+    N-vector are shared by all signals (ldw = 0); an nsig-vector is one lambda per signal (nw = 1, ldw = 1); an N x nsig matrix one
+    weight vector per signal.  With nsig == N a vector is the shared N-vector.  ValueError: any other shape."""
+    w = np.asarray(w, dtype=np.float64)
+    if w.ndim == 0 or w.shape == (1,):
+        return np.ascontiguousarray(w.reshape(1)), 1, 0
+    if w.shape == (N,):
+        return np.ascontiguousarray(w), N, 0
+    if w.shape == (nsig,):
+        return np.ascontiguousarray(w), 1, 1
+    if w.shape == (N, nsig):
+        return np.asfortranarray(w), N, max(N, 1)
+    raise ValueError(f"size(w) = {w.shape}: the weights are a scalar, {nsig} (one per signal), {N} (one per atom) or {(N, nsig)} numbers")
 
 
 class Context:
@@ -708,6 +726,64 @@ class Context:
         self.call("csmp_ista", vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64, ptr(w), i64(len(w)), ptr(idx0), ptr(val0),
                   i64(len(idx0)), i64(int(maxiter)), C.c_double(stepsize), int(bool(accel)), vp(x.data_ptr()), DEVICE, C.byref(rn))
         return rn.value
+
+    def _ista_batch_call(self, B, code, ldB, nsig, b_loc, w, X0, ldX0, X, ldX, x_loc, maxiter, stepsize, accel):
+        try:
+            w, nw, ldw = ista_batch_weights(w, self.N, nsig)
+        except ValueError as e:
+            raise CsmpError(EDIM, str(e)) from None
+        rn = np.zeros(max(nsig, 1), np.float64)
+        self.call("csmp_ista_batch", B, code, i64(ldB), i64(nsig), b_loc, ptr(w), i64(nw), i64(ldw), X0, i64(ldX0), i64(int(maxiter)),
+                  C.c_double(stepsize), int(bool(accel)), X, i64(ldX), x_loc, rn.ctypes.data_as(C.POINTER(C.c_double)))
+        return rn[:nsig]
+
+    def ista_batch(self, B, w, X0=None, maxiter=1024, stepsize=1e-2, accel=False):
+        """csmp_ista_batch on the host matrix B (M x nsig): ista (accel: fista) for every column, the signals of a group on shared
+        launches -- (X, Float64 N x nsig in Fortran order; resnorm float64[nsig]).  Column s and resnorm[s] are ista(B[:, s], w_s, ...)'s
+        bit for bit.  w: a scalar, an nsig-vector (one lambda per signal), an N-vector (shared by all signals) or an N x nsig matrix (a
+        weight vector per signal); with nsig == N a vector is the shared N-vector.  X0: None, or the dense N x nsig warm starts."""
+        B = np.asfortranarray(B)
+        if B.dtype not in (np.float32, np.float64):
+            B = B.astype(np.float64)
+        if B.ndim != 2 or B.shape[0] != self.M:
+            raise CsmpError(EDIM, f"size(B) = {B.shape} but size(A, 1) = {self.M}")
+        nsig = B.shape[1]
+        ld = max(self.N, 1)
+        X = np.zeros((ld, nsig), np.float64, order="F")
+        if X0 is not None:
+            X0 = np.asarray(X0, dtype=np.float64)
+            if X0.shape != (self.N, nsig):
+                raise CsmpError(EDIM, f"size(X0) = {X0.shape} but the warm starts are size(A, 2) x nsig = {(self.N, nsig)}")
+            X[:self.N] = X0  # (continued in place: X0 == X)
+        rn = self._ista_batch_call(ptr(B), dtype_code(B.dtype), max(self.M, 1), nsig, HOST, w, None if X0 is None else ptr(X), ld, ptr(X), ld, HOST,
+                                   maxiter, stepsize, accel)
+        return X[:self.N], rn
+
+    def ista_batch_device(self, B, w, X, X0=None, maxiter=1024, stepsize=1e-2, accel=False):
+        """torch CUDA tensors whose COLUMNS are the signals and the results, with bp_batch_device's stride rules: B (M, nsig) float32 /
+        float64 with stride (1, ldB >= M), X and (optionally) X0 (N, nsig) float64 with stride (1, ld >= N); X0 may be X itself (a run
+        continued in place) and must not overlap it otherwise.  w: as ista_batch, on the host.  Returns resnorm; the work is done when
+        the call returns."""
+        import torch
+        if not (B.is_cuda and B.dim() == 2 and B.shape[0] == self.M and B.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "B must be a CUDA matrix of size(A, 1) rows, float32 or float64")
+        nsig = B.shape[1]
+        ldB = B.stride(1) if nsig > 1 else max(self.M, 1)
+        if (self.M > 1 and B.stride(0) != 1) or ldB < self.M:
+            raise CsmpError(EDIM, "B must be column-major: unit row stride, a column stride of at least its row count")
+        lds = []
+        for name, T in (("X", X), ("X0", X0)):
+            if T is None:
+                lds.append(max(self.N, 1))
+                continue
+            if not (T.is_cuda and T.dim() == 2 and T.shape == (self.N, nsig) and T.dtype == torch.float64):
+                raise CsmpError(EDIM, f"{name} must be a CUDA float64 matrix of size(A, 2) rows and B's columns")
+            ld = T.stride(1) if nsig > 1 else max(self.N, 1)
+            if (self.N > 1 and T.stride(0) != 1) or ld < self.N:
+                raise CsmpError(EDIM, f"{name} must be column-major: unit row stride, a column stride of at least its row count")
+            lds.append(ld)
+        return self._ista_batch_call(vp(B.data_ptr()), F32 if B.dtype == torch.float32 else F64, ldB, nsig, DEVICE, w,
+                                     None if X0 is None else vp(X0.data_ptr()), lds[1], vp(X.data_ptr()), lds[0], DEVICE, maxiter, stepsize, accel)
 
     # ---- reweighted l1
     def ard_weights(self, x, w=None, eps=1e-2, iter=8):

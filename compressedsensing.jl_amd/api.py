@@ -189,6 +189,58 @@ def fista(A, b, lam_or_w, x=None, *, maxiter=1024, stepsize=1e-2):
     return _ista(A, b, lam_or_w, x, maxiter, stepsize, True)
 
 
+def _ista_batch(A, B, lam_or_w, X0, maxiter, stepsize, accel):
+    M, N, _ = _meta(A)
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] != M:
+        raise ValueError(f"size(B) = {B.shape} but size(A, 1) = {M}: B holds one signal per column")
+    nsig = B.shape[1]
+    w, _, _ = _lib.ista_batch_weights(lam_or_w, N, nsig)
+    if not np.all((w >= 0) & np.isfinite(w)):
+        raise ValueError("the weights have to be non-negative and finite")
+    if not maxiter >= 0:
+        raise ValueError(f"maxiter = {maxiter} has to be non-negative")
+    if not (stepsize > 0 and np.isfinite(stepsize)):
+        raise ValueError(f"stepsize = {stepsize} has to be positive and finite")
+    if X0 is not None:
+        if isinstance(X0, (list, tuple)):
+            if len(X0) != nsig or any(getattr(x, "n", None) != N for x in X0):
+                raise ValueError(f"X0 has to hold {nsig} SparseVectors of length {N}")
+            dense = np.zeros((N, nsig), np.float64, order="F")
+            for s, x in enumerate(X0):
+                dense[x.nzind, s] = x.nzval
+            X0 = dense
+        else:
+            X0 = np.asarray(X0, dtype=np.float64)
+            if X0.shape != (N, nsig):
+                raise ValueError(f"size(X0) = {X0.shape} but the warm starts are size(A, 2) x nsig = {(N, nsig)}")
+    D, tmp = _dict(A)
+    try:
+        X, _ = D.ctx.ista_batch(B, w, X0, maxiter=int(maxiter), stepsize=float(stepsize), accel=accel)
+        xs = []
+        for s in range(nsig):
+            nz = np.flatnonzero(X[:, s])  # dropzeros!, as ista
+            xs.append(SparseVector(N, nz, X[nz, s]))
+        return xs
+    finally:
+        if tmp:
+            D.close()
+
+
+def ista_batch(A, B, lam_or_w, X0=None, *, maxiter=1024, stepsize=1e-2):
+    """[ista(A, B[:, s], w_s, x0_s) for s in axes(B, 2)] on one GPU: up to eight signals take their iterations together, so the pass over
+    the dictionary for A'r is read once per step for all of them.  Every result is ista's bit for bit.  lam_or_w: a scalar, an
+    nsig-vector (one λ per signal: a regularisation path is the same b in every column), an N-vector (shared by all signals) or an
+    N x nsig matrix (a weight vector per signal); when nsig == N a vector is the shared N-vector.  X0: the warm starts, a list of
+    SparseVectors or a dense N x nsig matrix (not changed).  Returns a list of SparseVectors."""
+    return _ista_batch(A, B, lam_or_w, X0, maxiter, stepsize, False)
+
+
+def fista_batch(A, B, lam_or_w, X0=None, *, maxiter=1024, stepsize=1e-2):
+    """[fista(A, B[:, s], w_s, x0_s) for s in axes(B, 2)]: ista_batch with fista's acceleration, every result fista's bit for bit."""
+    return _ista_batch(A, B, lam_or_w, X0, maxiter, stepsize, True)
+
+
 # ------------------------------------------------------------------------------------ reweighted l1
 def candes_weights(x, eps=1e-2):
     """candes_weights!(w, x, ε): w_j = 1 / (|x_j| + ε) (src/basispursuit.jl:33-39), Float64[N]; x a vector or a SparseVector.  NaN or Inf

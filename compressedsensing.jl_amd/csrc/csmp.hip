@@ -65,6 +65,7 @@ using namespace csmp;
 #include "host/bp_batch.hpp"
 #include "host/bpd.hpp"
 #include "host/bpd_batch.hpp"
+#include "host/ista_batch.hpp"
 #include "host/sbl.hpp"
 #include "host/fsbl.hpp"
 #include "host/measure.hpp"

@@ -14,6 +14,7 @@
 //   k_bp_fold          the partials added in segment order
 //   k_bp_gemm          k_bp_gemv for up to eight right-hand sides per read of the matrix, and the group forms k_bp_update_group,
 //                      k_ista_axpy_group, k_ista_resum_group, k_bp_pq_group: csmp_bp_batch's step for all live members (host/bp_batch.hpp)
+//   k_ista_update_group  k_ista_update for the members of a group of csmp_ista_batch (host/ista_batch.hpp)
 //
 // Determinism: no atomics, no workgroup waits for another, every sum has a fixed order: the same bits on every run.
 #pragma once
@@ -401,6 +402,18 @@ __global__ __launch_bounds__(256) void k_bp_pq_group(int M, const BpGroup G) {
     const int m = (int)blockIdx.z;
     if (m >= G.n) return;
     bp_pq_body((int)blockIdx.x, G.b[m], G.r[m], G.g[m], M, G.p[m], G.q[m], G.e[m]);
+}
+// csmp_ista_batch's step (host/ista_batch.hpp): k_ista_update for every member of a group, x in z's place and y in u's.  Here every
+// member has weights of its own (W.w[m]: nw of them; the members of a batch with shared weights point at one set); alpha, beta and the
+// flags are the group's -- all members are at the same iteration.
+struct IstaGroupW {
+    const double* w[kBpGroupMax];
+};
+__global__ __launch_bounds__(kIstaThreads) void k_ista_update_group(const BpGroup G, const IstaGroupW W, int64_t nw, int64_t N, int64_t seg_len,
+                                                                    double alpha, double beta, int flags) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n) return;
+    ista_update_body(blockIdx.x, G.c[m], W.w[m], nw, G.z[m], G.u[m], N, seg_len, alpha, beta, flags, G.lidx[m], G.lval[m], G.seg_cnt[m]);
 }
 
 // res[0] = |u+ - u|^2, res[1] = |z+ - z|^2: the nseg <= 1024 partials of each, four per thread in order, then block_sum256

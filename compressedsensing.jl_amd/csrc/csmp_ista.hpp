@@ -68,13 +68,14 @@ __host__ __device__ __forceinline__ int ista_parts(unsigned n, int P) {
 // x+ = sign(u) max(|u| - w alpha, 0), u = y + 2 alpha c (src/basispursuit.jl:144,179); y+ = x+ + beta (x+ - x) under ISTA_ACCEL,
 // else y+ = x+.  An exact zero is a structural zero (dropzeros!, :180): it is not listed.  ISTA_INIT: x = y as it stands (the warm
 // start), no step.  ISTA_LIST_X: the list is that of x+ instead of y+ (the last iteration: the residual of the RESULT follows).
-__global__ __launch_bounds__(kIstaThreads) void k_ista_update(const double* __restrict__ c, const double* __restrict__ w, int64_t nw,
-                                                              double* __restrict__ x, double* __restrict__ y, int64_t N, int64_t seg_len,
-                                                              double alpha, double beta, int flags, int* __restrict__ lidx,
-                                                              double* __restrict__ lval, int* __restrict__ seg_cnt) {
+// The body is shared with k_ista_update_group (csmp_bp.hpp).  (seg: the workgroup's segment)
+__device__ __forceinline__ void ista_update_body(const unsigned seg, const double* __restrict__ c, const double* __restrict__ w, int64_t nw,
+                                                 double* __restrict__ x, double* __restrict__ y, int64_t N, int64_t seg_len, double alpha,
+                                                 double beta, int flags, int* __restrict__ lidx, double* __restrict__ lval,
+                                                 int* __restrict__ seg_cnt) {
     __shared__ int wcnt[kIstaThreads / kWave];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t j0 = (int64_t)blockIdx.x * seg_len, j1 = j0 + seg_len < N ? j0 + seg_len : N;
+    const int64_t j0 = (int64_t)seg * seg_len, j1 = j0 + seg_len < N ? j0 + seg_len : N;
     const double w0 = w[0];
     int64_t base = j0;
     for (int64_t jt = j0; jt < j1; jt += kIstaThreads) {
@@ -111,7 +112,13 @@ __global__ __launch_bounds__(kIstaThreads) void k_ista_update(const double* __re
         base += all;
         __syncthreads();
     }
-    if (tid == 0) seg_cnt[blockIdx.x] = (int)(base - j0);
+    if (tid == 0) seg_cnt[seg] = (int)(base - j0);
+}
+__global__ __launch_bounds__(kIstaThreads) void k_ista_update(const double* __restrict__ c, const double* __restrict__ w, int64_t nw,
+                                                              double* __restrict__ x, double* __restrict__ y, int64_t N, int64_t seg_len,
+                                                              double alpha, double beta, int flags, int* __restrict__ lidx,
+                                                              double* __restrict__ lval, int* __restrict__ seg_cnt) {
+    ista_update_body(blockIdx.x, c, w, nw, x, y, N, seg_len, alpha, beta, flags, lidx, lval, seg_cnt);
 }
 
 // part[p] = sum over workgroup p's share of the list of  val_t * A[:, idx_t]  (Float64 on the promoted entries), for the row block

@@ -220,6 +220,20 @@ struct BpdBatchBuf {
     int Mv = 0, P = 0, Mp = 0;
 };
 
+// csmp_ista_batch (host/ista_batch.hpp): what csmp_ista keeps per solve in IstaBuf, for each of R members of a group, in BpBatchBuf's
+// layout -- member m's share of an array starts m strides in: x and y (N each), the weights (N), the list of the next y (lidx, lval: N;
+// seg_cnt: kIstaMaxSegs), the axpy's partials (P Mv) and the list's length; nrm (||r||^2 per member) is read by the host in one piece.
+// b, r, c and the pass's partials are the solver slots'.  Apart from IstaBuf: csmp_ista's own buffers are neither read nor written.
+// Made on first use, sized by the dictionary and R: all or none.
+struct IstaBatchBuf {
+    double *xy = nullptr, *w = nullptr, *lval = nullptr, *part = nullptr, *nrm = nullptr;
+    int *lidx = nullptr, *seg_cnt = nullptr;
+    unsigned* nnz = nullptr;
+    int R = 0;       // members the buffers were made for (0: none)
+    int64_t N = 0;   // ... atoms
+    int Mv = 0, P = 0;
+};
+
 // sparse Bayesian learning (csmp_sbl.hpp, host/sbl.hpp): k_rowgram's partials of A Gamma A' and their sum G (M x M), the augmented
 // matrix [C | I], C = sigma2 I + G, that the blocked Cholesky turns into R beside R^-T (BpBuf's layout; R^-1 = L^-T in its rows from np
 // on), the M-vectors b and t = L^-1 b, the N-vectors gam, s, q and x, the partials and the verdicts, made on first use, sized by the
@@ -363,6 +377,7 @@ struct csmp_ctx {
     BpBatchBuf bpb;
     BpdBuf bpd;
     BpdBatchBuf bpdb;
+    IstaBatchBuf istab;
     SblBuf sbl;
     FsblBuf fsbl;
     // profiling

@@ -251,6 +251,7 @@ static int dict_forget(csmp_ctx* ctx) {
     bpb_free(ctx->bpb);
     bpd_free(ctx->bpd);
     bpdb_free(ctx->bpdb);
+    istab_free(ctx->istab);
     sbl_free(ctx->sbl);
     fsbl_free(ctx->fsbl);
     return CSMP_OK;

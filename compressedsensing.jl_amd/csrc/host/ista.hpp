@@ -90,6 +90,32 @@ static int ista_iterate(csmp_ctx* ctx, int64_t nw, int64_t maxiter, double steps
     return CSMP_OK;
 }
 
+// One solve on the active slot and the context's IstaBuf, b in place already (r = b, the residual of x = 0): the weights go up, then
+// the warm start -- x0, a dense N-vector where x0_kind says (null: x = 0) --, maxiter iterations, ||b - A x|| (resnorm may be null) and
+// x to the caller's vector at x_loc.  Returns with the stream drained.  csmp_ista and csmp_ista_batch's signal-by-signal path.
+static int ista_solve(csmp_ctx* ctx, const double* w, int64_t nw, const double* x0, hipMemcpyKind x0_kind, int64_t maxiter, double stepsize,
+                      int accel, double* x, int x_loc, double* resnorm) {
+    IstaBuf& t = ctx->ista;
+    HIPCHECK(hipMemcpyAsync(t.w, w, (size_t)nw * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    bool listed = false;  // the list (and r) belong to the current y
+    if (x0) {
+        HIPCHECK(hipMemcpyAsync(t.y, x0, (size_t)ctx->N * sizeof(double), x0_kind, ctx->stream));
+        CHECK(ista_launch_update(ctx, nw, 0.0, 0.0, ISTA_INIT | ISTA_LIST_X));
+        listed = true;
+    } else {
+        HIPCHECK(hipMemsetAsync(t.x, 0, (size_t)ctx->N * sizeof(double), ctx->stream));
+        HIPCHECK(hipMemsetAsync(t.y, 0, (size_t)ctx->N * sizeof(double), ctx->stream));
+    }
+    CHECK(ista_iterate(ctx, nw, maxiter, stepsize, accel, listed));
+    if (resnorm) {
+        if (listed) CHECK(ista_residual(ctx));
+        CHECK(residual_norm(ctx, resnorm));
+    }
+    HIPCHECK(hipMemcpyAsync(x, t.x, (size_t)ctx->N * sizeof(double), x_loc == CSMP_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(hipStreamSynchronize(ctx->stream));
+    return CSMP_OK;
+}
+
 extern "C" int csmp_ista(csmp_ctx* ctx, const void* b, int b_dtype, const double* w, int64_t nw, const int64_t* idx0, const double* val0,
                          int64_t nnz0, int64_t maxiter, double stepsize, int accel, double* x, int x_loc, double* resnorm) {
     if (!ctx) return CSMP_EINVAL;
@@ -122,29 +148,10 @@ extern "C" int csmp_ista(csmp_ctx* ctx, const void* b, int b_dtype, const double
         if (rc == CSMP_EHIP) return fail(ctx, CSMP_ENOMEM, "ista: no device memory for the iterates (" + ctx->err + ")");
         CHECK(rc);
     }
-    Solver& s = ctx->s;
-    IstaBuf& t = ctx->ista;
-    s.begun = false;
+    ctx->s.begun = false;
     if (x_loc == CSMP_DEVICE)
         CHECK(b_dtype == CSMP_F32 ? init_from_device_t<float>(ctx, (const float*)b) : init_from_device_t<double>(ctx, (const double*)b));
     else
         CHECK(upload_b(ctx, b, b_dtype));  // r = b: the residual of x = 0
-    HIPCHECK(hipMemcpyAsync(t.w, w, (size_t)nw * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    bool listed = false;  // the list (and r) belong to the current y
-    if (nnz0 > 0) {
-        HIPCHECK(hipMemcpyAsync(t.y, x0.data(), (size_t)ctx->N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        CHECK(ista_launch_update(ctx, nw, 0.0, 0.0, ISTA_INIT | ISTA_LIST_X));
-        listed = true;
-    } else {
-        HIPCHECK(hipMemsetAsync(t.x, 0, (size_t)ctx->N * sizeof(double), ctx->stream));
-        HIPCHECK(hipMemsetAsync(t.y, 0, (size_t)ctx->N * sizeof(double), ctx->stream));
-    }
-    CHECK(ista_iterate(ctx, nw, maxiter, stepsize, accel, listed));
-    if (resnorm) {
-        if (listed) CHECK(ista_residual(ctx));
-        CHECK(residual_norm(ctx, resnorm));
-    }
-    HIPCHECK(hipMemcpyAsync(x, t.x, (size_t)ctx->N * sizeof(double), x_loc == CSMP_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHECK(hipStreamSynchronize(ctx->stream));
-    return CSMP_OK;
+    return ista_solve(ctx, w, nw, nnz0 > 0 ? x0.data() : nullptr, hipMemcpyHostToDevice, maxiter, stepsize, accel, x, x_loc, resnorm);
 }

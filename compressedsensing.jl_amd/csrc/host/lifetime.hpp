@@ -123,6 +123,11 @@ static void bpdb_free(BpdBatchBuf& t) {
     t = BpdBatchBuf();
 }
 
+static void istab_free(IstaBatchBuf& t) {
+    dfree(t.xy); dfree(t.w); dfree(t.lval); dfree(t.part); dfree(t.nrm); dfree(t.lidx); dfree(t.seg_cnt); dfree(t.nnz);
+    t = IstaBatchBuf();
+}
+
 static void sbl_free(SblBuf& t) {
     dfree(t.Gpart); dfree(t.G); dfree(t.Gm); dfree(t.pivref); dfree(t.Dfac); dfree(t.vec); dfree(t.gam); dfree(t.s); dfree(t.q); dfree(t.x);
     dfree(t.part); dfree(t.info); dfree(t.st);
@@ -163,6 +168,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     bpb_free(ctx->bpb);
     bpd_free(ctx->bpd);
     bpdb_free(ctx->bpdb);
+    istab_free(ctx->istab);
     sbl_free(ctx->sbl);
     fsbl_free(ctx->fsbl);
     if (ctx->comm) (void)csmp_comm_free(ctx);

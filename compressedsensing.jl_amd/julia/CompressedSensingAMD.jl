@@ -184,6 +184,45 @@ fista(A::MatOrDict, b::AbstractVector, w::AbstractVector, x::AbstractVector = sp
 fista(A::MatOrDict, b::AbstractVector, λ::Real, x::AbstractVector = spzeros(size(A, 2)); maxiter::Int = 1024, stepsize::Real = 1e-2) =
     ista_call(A, b, Float64[λ], x, maxiter, stepsize, true)
 
+# [ista(A, B[:, s], w_s, x0_s) for s in axes(B, 2)]: up to eight signals take their iterations together on shared launches, every result
+# ista's bit for bit (csmp_ista_batch).  The weights: a λ or an N-vector shared by all signals, an nsig-vector of λs (one per signal; when
+# nsig == N a vector is the shared N-vector) or an N x nsig matrix (a weight vector per signal).  X0: the dense warm starts, N x nsig.
+function ista_batch_call(A::MatOrDict, B::AbstractMatrix, w::Array{Float64}, ldw::Int, X0::Union{Nothing,AbstractMatrix}, maxiter::Int,
+                         stepsize::Real, accel::Bool)
+    D = dict(A)
+    BB = B isa StridedMatrix && eltype(B) <: Union{Float32,Float64} && stride(B, 1) == 1 ? B : convert(Matrix{Float64}, B)
+    size(BB, 1) == size(D, 1) || throw(DimensionMismatch("size(B, 1) = $(size(BB, 1)) but size(A, 1) = $(size(D, 1))"))
+    nsig, N = size(BB, 2), size(D, 2)
+    X = zeros(Float64, N, nsig)
+    if X0 !== nothing
+        size(X0) == (N, nsig) || throw(DimensionMismatch("size(X0) = $(size(X0)) but the warm starts are $N x $nsig"))
+        copyto!(X, X0)  # (continued in place: X0 == X)
+    end
+    rn = zeros(Float64, nsig)
+    nw = ldw == 0 ? length(w) : size(w, 1)
+    GC.@preserve BB w X rn check(D, ccall((:csmp_ista_batch, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Ptr{Cdouble}, Int64, Int64, Ptr{Cdouble}, Int64, Int64, Cdouble, Cint, Ptr{Cdouble}, Int64,
+         Cint, Ptr{Cdouble}),
+        D.ctx, BB, dtype_code(eltype(BB)), max(stride(BB, 2), size(BB, 1)), nsig, CSMP_HOST, w, nw, ldw, X0 === nothing ? C_NULL : pointer(X), max(N, 1),
+        maxiter, stepsize, Cint(accel), X, max(N, 1), CSMP_HOST, rn))
+    return [sparse(X[:, s]) for s in 1:nsig]
+end
+function ista_batch_weights(A::MatOrDict, B::AbstractMatrix, w::AbstractVector)
+    N, nsig = size(A, 2), size(B, 2)
+    length(w) == N && return convert(Vector{Float64}, w), 0
+    length(w) == nsig && return reshape(convert(Vector{Float64}, w), 1, nsig), 1
+    throw(DimensionMismatch("length(w) = $(length(w)) is neither size(A, 2) = $N nor size(B, 2) = $nsig"))
+end
+function ista_batch_weights(A::MatOrDict, B::AbstractMatrix, W::AbstractMatrix)
+    size(W) == (size(A, 2), size(B, 2)) || throw(DimensionMismatch("size(W) = $(size(W)) but size(A, 2) x size(B, 2) = $((size(A, 2), size(B, 2)))"))
+    return convert(Matrix{Float64}, W), max(size(W, 1), 1)
+end
+ista_batch_weights(A::MatOrDict, B::AbstractMatrix, λ::Real) = (Float64[λ], 0)
+ista_batch(A::MatOrDict, B::AbstractMatrix, w::Union{Real,AbstractVecOrMat}, X0::Union{Nothing,AbstractMatrix} = nothing; maxiter::Int = 1024,
+           stepsize::Real = 1e-2) = ista_batch_call(A, B, ista_batch_weights(A, B, w)..., X0, maxiter, stepsize, false)
+fista_batch(A::MatOrDict, B::AbstractMatrix, w::Union{Real,AbstractVecOrMat}, X0::Union{Nothing,AbstractMatrix} = nothing; maxiter::Int = 1024,
+            stepsize::Real = 1e-2) = ista_batch_call(A, B, ista_batch_weights(A, B, w)..., X0, maxiter, stepsize, true)
+
 # ---------------------------------------------------------------------------------- reweighted l1
 # src/basispursuit.jl:18-74: candes_weights!, ard_weights! and basispursuit_reweighting with ista / fista as the solver of
 # ‖b - A x‖² + λ Σ w_j |x_j| (the loops around bp and bpd themselves: bp_candes / bp_ard and bpd_candes / bpd_ard below).

@@ -392,6 +392,39 @@ int csmp_ista(csmp_ctx *ctx, const void *b, int b_dtype, const double *w, int64_
               int64_t maxiter, double stepsize, int accel,
               double *x, int x_loc, double *resnorm);
 
+/* ista_batch: csmp_ista for every column of B on shared launches.  The pass over the dictionary for c = A'r is the same for every
+ * signal: a group of up to eight signals (the groups of csmp_mp_batch and csmp_bp_batch: csmp_tune group_max / group_wide apply) takes
+ * its iterations together, four launches a step however many members it has -- one launch each for the residual's two steps
+ * (r = b - A y over every member's own list), one shared pass over A, one launch for the update.  Every signal runs exactly maxiter
+ * iterations (there is no stopping rule), so the signals are taken in ascending order, a group at a time, and nothing waits for the
+ * device between a group's first launch and its results.
+ * Contract: column s of X and resnorm[s] are those of csmp_ista(ctx, B[:, s], w_s, x0_s, maxiter, stepsize, accel, ...), BIT FOR BIT,
+ * whatever nsig and the group sizes are.
+ * B: size(A,1) x nsig, column-major, leading dimension ldB >= size(A,1), CSMP_F32 or CSMP_F64, on the host or the device (b_loc).
+ * X: size(A,2) x nsig doubles, leading dimension ldX >= size(A,2), on the host or the device (x_loc); column s receives the dense
+ * result of signal s, rows beyond size(A,2) are not touched.
+ * w, nw, ldw: a host array; nw = 1 (one weight for every atom) or size(A,2) (one per atom), as csmp_ista.  ldw = 0: the nw weights
+ * are shared by all signals.  ldw >= nw: w is nw x nsig with leading dimension ldw and column s belongs to signal s -- one lambda
+ * per signal (nw = 1, ldw = 1) or one weight vector per signal: a regularisation path is the same b in every column.
+ * X0, ldX0: NULL starts every signal from zero.  Otherwise a dense size(A,2) x nsig matrix of doubles where X lives (x_loc), leading
+ * dimension ldX0 >= size(A,2): column s is the warm start of signal s, the dense vector csmp_ista builds from idx0 / val0.
+ * X0 == X with ldX0 == ldX continues a run in place; any other overlap of X0 and X is the caller's error and is not detected.
+ * resnorm: a host array of nsig entries, or NULL.  maxiter = 0 returns the warm start (or zeros) and resnorm[s] = ||b_s - A x0_s||,
+ * which is ||b_s|| for a zero start.  nsig = 0: CSMP_OK, nothing is touched.
+ * A dictionary without a shared pass (csmp_sweep_config: group 0), CSMP_OPT_SCREENED_SWEEP switched on and nsig = 1 take csmp_ista's
+ * own launches signal by signal: the same outputs.
+ * Memory beside csmp_ista's, kept by the context until csmp_set_dictionary: per member of a group 3 size(A,2) + the list
+ * (1.5 size(A,2)) doubles and the residual's partials -- 18 MiB + 128 MiB for eight members at 4096 x 65536.
+ * CSMP_EINVAL: nsig < 0, null pointers, a dtype / location that is neither, accel other than 0 or 1, maxiter < 0, a stepsize that is
+ * not positive and finite, a negative or non-finite weight (in any column), ldw < 0 or 0 < ldw < nw.  CSMP_EDIM: ldB < size(A,1),
+ * ldX < size(A,2), ldX0 < size(A,2), nw other than 1 or size(A,2).  CSMP_ESTATE: no dictionary, or a host-streamed one (as csmp_ista).
+ * CSMP_ENOMEM: a buffer could not be allocated; no partial buffers are left behind and the context stays usable.  Everything is
+ * validated before any device work.  A refused call writes nothing. */
+int csmp_ista_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc,
+                    const double *w, int64_t nw, int64_t ldw, const double *X0, int64_t ldX0,
+                    int64_t maxiter, double stepsize, int accel, double *X, int64_t ldX, int x_loc,
+                    double *resnorm);
+
 /* ------------------------------------------------------------------ reweighted l1
  * candes_weights! / ard_weights! / basispursuit_reweighting: src/basispursuit.jl:18-74 (bp_candes, bp_ard; bpd_candes, bpd_ard :102-124),
  * with ista / fista as the inner solver (the reference's own inner solvers, bp and bpd, are csmp_bp and csmp_bpd below: neither needs
