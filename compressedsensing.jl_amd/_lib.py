@@ -103,6 +103,10 @@ SIGNATURES = {
     "csmp_fsbl": (C.c_int, [vp, vp, C.c_int, C.c_double, i64, C.c_double, vp, vp, vp, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(C.c_int)]),
     "csmp_rmps": (C.c_int, [vp, vp, C.c_int, C.c_double, i64, i64, i64, C.c_double, vp, vp, vp, C.c_int, vp, i64, C.POINTER(i64),
                             C.POINTER(C.c_int)]),
+    "csmp_fsbl_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, vp, i64, i64, C.c_double, vp, i64, vp, i64, vp, i64, C.c_int, vp, i64,
+                                  C.POINTER(i64), C.POINTER(C.c_int)]),
+    "csmp_rmps_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, vp, i64, i64, i64, i64, C.c_double, vp, i64, vp, i64, vp, i64, C.c_int, vp,
+                                  i64, C.POINTER(i64), C.POINTER(C.c_int)]),
     "csmp_colnorms": (C.c_int, [vp, vp, C.c_int]),
     "csmp_cumbabel": (C.c_int, [vp, i64, C.c_int, vp, vp]),
     "csmp_sweep": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -1205,6 +1209,104 @@ class Context:
                 raise CsmpError(EDIM, "x and alpha must be contiguous CUDA float64 vectors of length size(A, 2)")
         return ((vp(b.data_ptr()), F32 if b.dtype == torch.float32 else F64), vp(alpha_in.data_ptr() if alpha_in is not None else 0),
                 vp(x.data_ptr()), vp(alpha_out.data_ptr() if alpha_out is not None else 0))
+
+    # ---- greedy sparse Bayesian learning for many signals
+    def _greedy_batch(self, name, B, code, ldB, nsig, b_loc, sigma2, caps, min_increase, alpha_in, ld_in, X, ldX, alpha_out, ld_out, x_loc,
+                      history_cap, applied):
+        """csmp_fsbl_batch / csmp_rmps_batch: caps are the call's iteration caps in the prototype's order; returns info without alpha"""
+        s2 = np.ascontiguousarray(np.atleast_1d(np.asarray(sigma2, dtype=np.float64)))
+        if s2.ndim != 1:
+            raise CsmpError(EDIM, "sigma2 has to be a scalar or one value per signal")
+        cap = max(int(history_cap), 0)
+        hist = np.zeros((max(nsig, 1), max(cap, 1), 2), np.int64)
+        it, fl = np.zeros(max(nsig, 1), np.int64), np.zeros(max(nsig, 1), np.int32)
+        self.call(name, B, code, i64(ldB), i64(nsig), b_loc, ptr(s2), i64(len(s2)), *[i64(int(c)) for c in caps], C.c_double(min_increase),
+                  alpha_in, i64(ld_in), X, i64(ldX), alpha_out, i64(ld_out), x_loc, ptr(hist) if cap > 0 else None, i64(cap),
+                  it.ctypes.data_as(C.POINTER(i64)), fl.ctypes.data_as(C.POINTER(C.c_int)))
+        info = {"iterations": it[:nsig], "converged": (fl[:nsig] & FSBL_CONVERGED) != 0, "history": []}
+        for s in range(nsig):
+            one = self._history({}, hist[s], cap, int(it[s]) if applied else None)
+            info["history"].append(one["history"])
+        return info
+
+    def _greedy_batch_host(self, name, B, sigma2, caps, min_increase, alpha, history_cap, applied):
+        B = np.asfortranarray(B)
+        if B.dtype not in (np.float32, np.float64):
+            B = B.astype(np.float64)
+        if B.ndim != 2 or B.shape[0] != self.M:
+            raise CsmpError(EDIM, f"size(B) = {B.shape} but size(A, 1) = {self.M}")
+        nsig = B.shape[1]
+        ld = max(self.N, 1)
+        X = np.zeros((ld, nsig), np.float64, order="F")
+        a = np.zeros((ld, nsig), np.float64, order="F")
+        if alpha is not None:
+            alpha = np.asarray(alpha, dtype=np.float64)
+            if alpha.shape != (self.N, nsig):
+                raise CsmpError(EDIM, f"size(alpha) = {alpha.shape} but the warm starts are size(A, 2) x nsig = {(self.N, nsig)}")
+            a[:self.N] = alpha  # (alpha_out is alpha_in)
+        info = self._greedy_batch(name, ptr(B), dtype_code(B.dtype), max(self.M, 1), nsig, HOST, sigma2, caps, min_increase,
+                                  None if alpha is None else ptr(a), ld, ptr(X), ld, ptr(a), ld, HOST, history_cap, applied)
+        info["alpha"] = a[:self.N]
+        return X[:self.N], info
+
+    def fsbl_batch(self, B, sigma2, maxiter=None, min_increase=1e-6, alpha=None, history_cap=None):
+        """csmp_fsbl_batch on the host matrix B (M x nsig): fsbl for every column, the signals of a group in lockstep on shared launches --
+        (X, Float64 N x nsig in Fortran order; info = iterations int64[nsig], converged bool[nsig], alpha N x nsig, history: a list of
+        (action, index) pairs per signal).  Column s and signal s's info are fsbl(B[:, s], sigma2_s, ...)'s bit for bit.  sigma2: a scalar or
+        one value per signal.  alpha: None, or the N x nsig prior precisions to start from (+inf: inactive).  The defaults are fsbl's."""
+        maxiter = 2 * self.N if maxiter is None else int(maxiter)
+        cap = max(maxiter, 0) if history_cap is None else int(history_cap)
+        return self._greedy_batch_host("csmp_fsbl_batch", B, sigma2, (maxiter,), min_increase, alpha, cap, False)
+
+    def rmps_batch(self, B, sigma2, maxiter=None, maxiter_acquisition=None, maxiter_deletion=None, min_increase=1e-6, alpha=None,
+                   history_cap=None):
+        """csmp_rmps_batch on the host matrix B: as fsbl_batch, for rmps; the three caps default to M; iterations counts the applied steps.
+        history_cap=None: the whole histories (a batch with a run longer than 4 N steps is run again with the room it needs)."""
+        caps = tuple(self.M if c is None else int(c) for c in (maxiter, maxiter_acquisition, maxiter_deletion))
+        cap = 4 * self.N if history_cap is None else int(history_cap)
+        X, info = self._greedy_batch_host("csmp_rmps_batch", B, sigma2, caps, min_increase, alpha, cap, True)
+        if history_cap is None and len(info["iterations"]) and int(info["iterations"].max()) > cap:
+            cap = int(info["iterations"].max())
+            X, info = self._greedy_batch_host("csmp_rmps_batch", B, sigma2, caps, min_increase, alpha, cap, True)
+        return X, info
+
+    def _greedy_batch_device(self, B, X, alpha_in, alpha_out):
+        import torch
+        if not (B.is_cuda and B.dim() == 2 and B.shape[0] == self.M and B.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "B must be a CUDA matrix of size(A, 1) rows, float32 or float64")
+        nsig = B.shape[1]
+        ldB = B.stride(1) if nsig > 1 else max(self.M, 1)
+        if (self.M > 1 and B.stride(0) != 1) or ldB < self.M:
+            raise CsmpError(EDIM, "B must be column-major: unit row stride, a column stride of at least its row count")
+        lds = []
+        for name, T in (("X", X), ("alpha_in", alpha_in), ("alpha_out", alpha_out)):
+            if T is None:
+                lds.append(max(self.N, 1))
+                continue
+            if not (T.is_cuda and T.dim() == 2 and T.shape == (self.N, nsig) and T.dtype == torch.float64):
+                raise CsmpError(EDIM, f"{name} must be a CUDA float64 matrix of size(A, 2) rows and B's columns")
+            ld = T.stride(1) if nsig > 1 else max(self.N, 1)
+            if (self.N > 1 and T.stride(0) != 1) or ld < self.N:
+                raise CsmpError(EDIM, f"{name} must be column-major: unit row stride, a column stride of at least its row count")
+            lds.append(ld)
+        p = [None if T is None else vp(T.data_ptr()) for T in (alpha_in, X, alpha_out)]
+        return (vp(B.data_ptr()), F32 if B.dtype == torch.float32 else F64, ldB, nsig, DEVICE), (p[0], lds[1], p[1], lds[0], p[2], lds[2], DEVICE)
+
+    def fsbl_batch_device(self, B, sigma2, X, alpha_in=None, alpha_out=None, maxiter=None, min_increase=1e-6, history_cap=0):
+        """torch CUDA tensors whose COLUMNS are the signals and the results, with bp_batch_device's stride rules: B (M, nsig) float32 /
+        float64 with stride (1, ldB >= M); X receives the results, alpha_in (None: all +inf) and alpha_out (None: not wanted; may be
+        alpha_in) are (N, nsig) float64 with stride (1, ld >= N).  sigma2: on the host.  Returns info without alpha; the work is done when
+        the call returns."""
+        b, x = self._greedy_batch_device(B, X, alpha_in, alpha_out)
+        maxiter = 2 * self.N if maxiter is None else int(maxiter)
+        return self._greedy_batch("csmp_fsbl_batch", *b, sigma2, (maxiter,), min_increase, *x, history_cap, False)
+
+    def rmps_batch_device(self, B, sigma2, X, alpha_in=None, alpha_out=None, maxiter=None, maxiter_acquisition=None, maxiter_deletion=None,
+                          min_increase=1e-6, history_cap=0):
+        """as fsbl_batch_device, for csmp_rmps_batch"""
+        b, x = self._greedy_batch_device(B, X, alpha_in, alpha_out)
+        caps = tuple(self.M if c is None else int(c) for c in (maxiter, maxiter_acquisition, maxiter_deletion))
+        return self._greedy_batch("csmp_rmps_batch", *b, sigma2, caps, min_increase, *x, history_cap, True)
 
     def fsbl_score(self, alpha, S, Q, mode):
         """csmp_fsbl_score (csmp_internal.h): (values Float64[N], pick, value, action) of one N-pass on a state of the caller's; mode: a key

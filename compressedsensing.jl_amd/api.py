@@ -649,6 +649,60 @@ def rmps(A, b, sigma2, *, maxiter=None, maxiter_acquisition=None, maxiter_deleti
             D.close()
 
 
+def _fsbl_batch(who, A, B, sigma2, caps, min_increase, alpha, return_info):
+    M, N, _ = _meta(A)
+    if isinstance(sigma2, (bool, np.bool_)):  # the reference's rmps(A, b, Val(true), ...)
+        raise NotImplementedError(f"{who}: the σ²-optimising form (Val(true)) is not served: pass the noise variance σ²")
+    if np.ndim(sigma2) > 1:
+        raise NotImplementedError(f"{who}: only scalar noise variances σ² are served (one, or one per signal), not a covariance matrix Σ")
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] != M:
+        raise ValueError(f"size(B) = {B.shape} but size(A, 1) = {M}: B holds one signal per column")
+    nsig = B.shape[1]
+    s2 = np.asarray(sigma2, dtype=np.float64)
+    if s2.ndim == 1 and s2.shape[0] != nsig:
+        raise ValueError(f"length(σ²) = {s2.shape[0]} but B holds {nsig} signals")
+    if not np.all((s2 > 0) & np.isfinite(s2)):
+        raise ValueError(f"σ² = {sigma2} has to be positive and finite")
+    if not min_increase >= 0:
+        raise ValueError(f"min_increase = {min_increase} has to be non-negative")
+    for name, c in caps.items():
+        if c is not None and (not _is_int(c) or c < 1):
+            raise ValueError(f"{name} = {c} has to be at least 1")
+    if alpha is not None:
+        alpha = np.asarray(alpha, dtype=np.float64)
+        if alpha.shape != (N, nsig) or not np.all(alpha > 0):
+            raise ValueError("alpha has to be size(A, 2) x nsig with every entry positive, or +inf for an inactive atom")
+    D, tmp = _dict(A)
+    try:
+        X, info = getattr(D.ctx, who)(B, s2, *caps.values(), float(min_increase), alpha)
+        xs = []
+        for s in range(nsig):
+            nz = np.flatnonzero(X[:, s])
+            xs.append(SparseVector(N, nz, X[nz, s]))
+        return (xs, info) if return_info else xs
+    finally:
+        if tmp:
+            D.close()
+
+
+def fsbl_batch(A, B, sigma2, *, maxiter=None, min_increase=1e-6, alpha=None, return_info=False):
+    """[fsbl(A, B[:, s], σ²_s) for s in axes(B, 2)] on one GPU: up to eight signals take their greedy steps in lockstep, so the product
+    sweep of a step reads the dictionary once for all of them (include/csmp.h, csmp_fsbl_batch).  Every result is fsbl's bit for bit.
+    sigma2: one noise variance, or one per signal.  alpha: None, or the N x nsig prior precisions to start from (+inf: inactive).
+    Returns a list of SparseVectors; return_info=True: (xs, info) with the per-signal iterations, converged, alpha (N x nsig) and
+    history.  A noise covariance matrix raises NotImplementedError."""
+    return _fsbl_batch("fsbl_batch", A, B, sigma2, {"maxiter": maxiter}, min_increase, alpha, return_info)
+
+
+def rmps_batch(A, B, sigma2, *, maxiter=None, maxiter_acquisition=None, maxiter_deletion=None, min_increase=1e-6, alpha=None,
+               return_info=False):
+    """[rmps(A, B[:, s], σ²_s) for s in axes(B, 2)] on one GPU: as fsbl_batch, every result rmps's bit for bit.  A noise covariance matrix
+    and the σ²-optimising form (σ² = True) raise NotImplementedError."""
+    return _fsbl_batch("rmps_batch", A, B, sigma2, {"maxiter": maxiter, "maxiter_acquisition": maxiter_acquisition,
+                                                    "maxiter_deletion": maxiter_deletion}, min_increase, alpha, return_info)
+
+
 # ------------------------------------------------------------------------------------ dictionary analysis
 def colnorms(A):
     """colnorms(A) = [norm(a) for a in eachcol(A)] (src/util.jl:2), Float64."""

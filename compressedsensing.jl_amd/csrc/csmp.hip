@@ -68,5 +68,6 @@ using namespace csmp;
 #include "host/ista_batch.hpp"
 #include "host/sbl.hpp"
 #include "host/fsbl.hpp"
+#include "host/fsbl_batch.hpp"
 #include "host/measure.hpp"
 #include "host/rccl.hpp"

@@ -10,6 +10,9 @@
 //   k_fsbl_rank1   C^-1 -= v v' / den, streaming, every element from the same two operands in the same order
 //   the product sweep (csmp_kernels.hpp, unchanged) w = A'v
 //   k_fsbl_x       x_j = Q_j / alpha_j on the active atoms, 0 elsewhere
+//   k_fsbl_score_group, k_fsbl_pick_group, k_fsbl_col_group, k_fsbl_gemv_group, k_fsbl_rank1_group
+//                  the same work for every member of a lockstep group of csmp_fsbl_batch / csmp_rmps_batch in ONE launch each: the
+//                  single kernels' bodies (fsbl_*_body) on the member's own buffers, the member on the grid's third axis
 //
 // Determinism: no atomics, no workgroup waits for another, every fold has a fixed order: the same bits on every run.
 #pragma once
@@ -72,15 +75,16 @@ __device__ __forceinline__ bool fsbl_better(bool MIN, double v, long long i, dou
 // first and are stored.  Then the atom's value (vals, where not NULL, receives it), thread bests in index order, the wave's and the
 // workgroup's by fsbl_better.  pval[g] / pidx[g]: the workgroup's best; pidx[g] = -1 where a value is NaN or an infinite maximum.
 // FSBL_MODE_NONE: the pending update alone.
-__global__ __launch_bounds__(256) void k_fsbl_score(const double* __restrict__ alpha, double* __restrict__ S, double* __restrict__ Q,
-                                                    const double* __restrict__ w, const FsblRec* __restrict__ rec, int64_t N, int64_t per, int mode,
-                                                    double* __restrict__ vals, double* __restrict__ pval, long long* __restrict__ pidx) {
+// blk: the workgroup's index g.
+__device__ __forceinline__ void fsbl_score_body(const int blk, const double* __restrict__ alpha, double* __restrict__ S, double* __restrict__ Q,
+                                                const double* __restrict__ w, const FsblRec* __restrict__ rec, int64_t N, int64_t per, int mode,
+                                                double* __restrict__ vals, double* __restrict__ pval, long long* __restrict__ pidx) {
     __shared__ double sv[4];
     __shared__ long long si[4];
     const bool pend = rec->pending != 0;
     const double den = rec->den, Qi = rec->Qi;
     const bool MIN = mode == FSBL_MODE_RMP_DEL;
-    const int64_t j0 = (int64_t)blockIdx.x * per, j1 = j0 + per < N ? j0 + per : N;
+    const int64_t j0 = (int64_t)blk * per, j1 = j0 + per < N ? j0 + per : N;
     double bv = MIN ? __builtin_inf() : -__builtin_inf();
     long long bi = 0x7fffffffffffffffLL;
     int bad = 0;
@@ -123,9 +127,14 @@ __global__ __launch_bounds__(256) void k_fsbl_score(const double* __restrict__ a
                 bv = sv[k];
                 bi = si[k];
             }
-        pval[blockIdx.x] = bv;
-        pidx[blockIdx.x] = anybad ? -1 : bi;
+        pval[blk] = bv;
+        pidx[blk] = anybad ? -1 : bi;
     }
+}
+__global__ __launch_bounds__(256) void k_fsbl_score(const double* __restrict__ alpha, double* __restrict__ S, double* __restrict__ Q,
+                                                    const double* __restrict__ w, const FsblRec* __restrict__ rec, int64_t N, int64_t per, int mode,
+                                                    double* __restrict__ vals, double* __restrict__ pval, long long* __restrict__ pidx) {
+    fsbl_score_body((int)blockIdx.x, alpha, S, Q, w, rec, N, per, mode, vals, pval, pidx);
 }
 
 // One workgroup.  force_i < 0: the nparts partials folded (thread t holds partial t; a workgroup's atoms lie below the next one's, so the
@@ -133,9 +142,9 @@ __global__ __launch_bounds__(256) void k_fsbl_score(const double* __restrict__ a
 // delete where the minimum is < 1 (FSBL_MODE_RMP_DEL), re-estimate where it is > 0 (FSBL_MODE_UPD), whichever of the three matches the
 // atom where it is > 0 (FSBL_MODE_ALL) -- with alpha_i written and the record filled.  force_i >= 0: the rank-one step of atom force_i
 // with the given gamma, alpha untouched (the warm start's replay, the measurement hooks).
-__global__ __launch_bounds__(256) void k_fsbl_pick(const double* __restrict__ pval, const long long* __restrict__ pidx, int nparts, int mode,
-                                                   double* __restrict__ alpha, const double* __restrict__ S, const double* __restrict__ Q,
-                                                   long long force_i, double force_gamma, FsblRec* __restrict__ rec) {
+__device__ __forceinline__ void fsbl_pick_body(const double* __restrict__ pval, const long long* __restrict__ pidx, int nparts, int mode,
+                                               double* __restrict__ alpha, const double* __restrict__ S, const double* __restrict__ Q,
+                                               long long force_i, double force_gamma, FsblRec* __restrict__ rec) {
     __shared__ double sv[4];
     __shared__ long long si[4];
     FsblRec r;
@@ -220,16 +229,21 @@ __global__ __launch_bounds__(256) void k_fsbl_pick(const double* __restrict__ pv
     r.pending = r.action != FSBL_ACT_NONE ? 1 : 0;
     *rec = r;
 }
+__global__ __launch_bounds__(256) void k_fsbl_pick(const double* __restrict__ pval, const long long* __restrict__ pidx, int nparts, int mode,
+                                                   double* __restrict__ alpha, const double* __restrict__ S, const double* __restrict__ Q,
+                                                   long long force_i, double force_gamma, FsblRec* __restrict__ rec) {
+    fsbl_pick_body(pval, pidx, nparts, mode, alpha, S, Q, force_i, force_gamma, rec);
+}
 
 // col[r] = A[r, i] as a double for r < M, i = rec->i (what lies beyond M in col is zero and stays so).  VEC: the columns of A start on
 // 16-byte boundaries -- 16-byte loads over the whole vectors of the column, the rest by elements.
 template <typename TA, bool VEC>
-__global__ __launch_bounds__(256) void k_fsbl_col(const TA* __restrict__ A, int64_t ld, int M, const FsblRec* __restrict__ rec,
-                                                  double* __restrict__ col) {
+__device__ __forceinline__ void fsbl_col_body(const int blk, const TA* __restrict__ A, int64_t ld, int M, const FsblRec* __restrict__ rec,
+                                              double* __restrict__ col) {
     constexpr int PERV = 16 / (int)sizeof(TA);
     typedef TA tav __attribute__((ext_vector_type(PERV)));
     const TA* a = A + rec->i * ld;
-    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int t = blk * 256 + threadIdx.x;
     if (VEC) {
         const int r0 = t * PERV;
         if (r0 + PERV <= M) {
@@ -242,20 +256,24 @@ __global__ __launch_bounds__(256) void k_fsbl_col(const TA* __restrict__ A, int6
     } else {
 #pragma unroll
         for (int c = 0; c < PERV; ++c) {
-            const int r = blockIdx.x * 256 * PERV + c * 256 + threadIdx.x;
+            const int r = blk * 256 * PERV + c * 256 + threadIdx.x;
             if (r < M) col[r] = (double)a[r];
         }
     }
+}
+template <typename TA, bool VEC>
+__global__ __launch_bounds__(256) void k_fsbl_col(const TA* __restrict__ A, int64_t ld, int M, const FsblRec* __restrict__ rec,
+                                                  double* __restrict__ col) {
+    fsbl_col_body<TA, VEC>((int)blockIdx.x, A, ld, M, rec, col);
 }
 
 // Ci[r, c] -= v[r] v[c] / den (den = rec->den), Ci with the even leading dimension ldc >= M: workgroup (c, y) takes the rows
 // 512 y .. 512 y + 511 of column c, a thread two of them with one 16-byte load and store.  The product is rounded (commutative: the
 // element (c, r) forms the same), divided, subtracted -- no contraction -- so the matrix stays exactly symmetric.  v is zero from M on.
-__global__ __launch_bounds__(256) void k_fsbl_rank1(double* __restrict__ Ci, int64_t ldc, const double* __restrict__ v,
-                                                    const FsblRec* __restrict__ rec) {
+__device__ __forceinline__ void fsbl_rank1_body(const int64_t c, const int by, double* __restrict__ Ci, int64_t ldc, const double* __restrict__ v,
+                                                const FsblRec* __restrict__ rec) {
     typedef double d2 __attribute__((ext_vector_type(2)));
-    const int64_t c = blockIdx.x;
-    const int64_t r = ((int64_t)blockIdx.y * 256 + threadIdx.x) * 2;
+    const int64_t r = ((int64_t)by * 256 + threadIdx.x) * 2;
     if (r >= ldc) return;
     const double den = rec->den, vc = v[c];
     const d2 vr = *reinterpret_cast<const d2*>(v + r);
@@ -264,6 +282,10 @@ __global__ __launch_bounds__(256) void k_fsbl_rank1(double* __restrict__ Ci, int
     x[0] = __dsub_rn(x[0], __ddiv_rn(__dmul_rn(vr[0], vc), den));
     x[1] = __dsub_rn(x[1], __ddiv_rn(__dmul_rn(vr[1], vc), den));
     *p = x;
+}
+__global__ __launch_bounds__(256) void k_fsbl_rank1(double* __restrict__ Ci, int64_t ldc, const double* __restrict__ v,
+                                                    const FsblRec* __restrict__ rec) {
+    fsbl_rank1_body((int64_t)blockIdx.x, (int)blockIdx.y, Ci, ldc, v, rec);
 }
 
 // Ci = I / sigma2 over the M x M block, zero in the padding rows
@@ -289,6 +311,68 @@ __global__ __launch_bounds__(256) void k_fsbl_x(const double* __restrict__ alpha
     if (j >= N) return;
     const double a = alpha[j];
     x[j] = a < __builtin_inf() ? Q[j] / a : 0.0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The group forms of csmp_fsbl_batch / csmp_rmps_batch (host/fsbl_batch.hpp): ONE launch does a kernel's work for every member of a
+// lockstep group that takes part in the tick.  The member is the grid's third axis; its pointers, the mode of its N-pass and a forced
+// (atom, gamma) come from this kernel-argument struct, by value.  Every member's workgroups run the single kernels' bodies above on the
+// member's own buffers: per member the arithmetic and its order are the single solve's.  turn[m] = 0: the member takes the N-pass only
+// (the pending update of a member that is finishing) and leaves k_fsbl_pick_group and the step's kernels at once; the step's kernels
+// -- k_fsbl_col_group, k_fsbl_gemv_group, k_fsbl_rank1_group -- also leave where the member's device record holds no action, so a
+// tick's launches go out without the host reading a record in between.
+struct FsblGroup {
+    int n;
+    int mode[kBpGroupMax];              // FSBL_MODE_* of the member's N-pass
+    int turn[kBpGroupMax];              // 1: the member picks and, where its record says so, steps
+    long long force_i[kBpGroupMax];     // >= 0: the forced record of the warm start's replay
+    double force_gamma[kBpGroupMax];
+    double *alpha[kBpGroupMax], *S[kBpGroupMax], *Q[kBpGroupMax], *w[kBpGroupMax], *pval[kBpGroupMax];
+    long long* pidx[kBpGroupMax];
+    FsblRec* rec[kBpGroupMax];
+    double *Ci[kBpGroupMax], *col[kBpGroupMax], *v[kBpGroupMax];  // C^-1, a_i and v = C^-1 a_i
+};
+static_assert(sizeof(FsblGroup) <= 4096, "kernel arguments");
+__global__ __launch_bounds__(256) void k_fsbl_score_group(const FsblGroup G, int64_t N, int64_t per) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n) return;
+    fsbl_score_body((int)blockIdx.x, G.alpha[m], G.S[m], G.Q[m], G.w[m], G.rec[m], N, per, G.mode[m], nullptr, G.pval[m], G.pidx[m]);
+}
+__global__ __launch_bounds__(256) void k_fsbl_pick_group(const FsblGroup G, int nparts) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n || !G.turn[m]) return;
+    fsbl_pick_body(G.pval[m], G.pidx[m], nparts, G.mode[m], G.alpha[m], G.S[m], G.Q[m], G.force_i[m], G.force_gamma[m], G.rec[m]);
+}
+template <typename TA, bool VEC>
+__global__ __launch_bounds__(256) void k_fsbl_col_group(const TA* __restrict__ A, int64_t ld, int M, const FsblGroup G) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n || !G.turn[m] || !G.rec[m]->pending) return;
+    fsbl_col_body<TA, VEC>((int)blockIdx.x, A, ld, M, G.rec[m], G.col[m]);
+}
+// v_m = C_m^-1 a_m: k_bp_gemv's BP_FULL arithmetic for every member, one matrix per member -- a wave per output, the lane partials over
+// t = lane in steps of 128 on the chains a0 and a1, the tail into a0, a0 + a1, the butterfly 32 .. 1.
+__global__ __launch_bounds__(256) void k_fsbl_gemv_group(int64_t ldc, int M, const FsblGroup G) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n || !G.turn[m] || !G.rec[m]->pending) return;
+    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= M) return;
+    const double* __restrict__ col = G.Ci[m] + (int64_t)c * ldc;
+    const double* __restrict__ x = G.col[m];
+    double a0 = 0.0, a1 = 0.0;
+    int t = lane;
+    for (; t + 64 < M; t += 128) {
+        a0 = fma(col[t], x[t], a0);
+        a1 = fma(col[t + 64], x[t + 64], a1);
+    }
+    if (t < M) a0 = fma(col[t], x[t], a0);
+    double a = a0 + a1;
+    for (int s = 32; s >= 1; s >>= 1) a += shx(a, s);
+    if (lane == 0) G.v[m][c] = a;
+}
+__global__ __launch_bounds__(256) void k_fsbl_rank1_group(int64_t ldc, const FsblGroup G) {
+    const int m = (int)blockIdx.z;
+    if (m >= G.n || !G.turn[m] || !G.rec[m]->pending) return;
+    fsbl_rank1_body((int64_t)blockIdx.x, (int)blockIdx.y, G.Ci[m], ldc, G.v[m], G.rec[m]);
 }
 
 }  // namespace csmp

@@ -263,6 +263,23 @@ struct FsblBuf {
     int64_t ldc = 0;
 };
 
+// csmp_fsbl_batch / csmp_rmps_batch (host/fsbl_batch.hpp): what csmp_fsbl keeps per solve in FsblBuf, for each of R members of a lockstep
+// group -- member m's share of an array starts m strides in: Ci (ldc M), the two M-vectors (2 Mp, zero beyond M), alpha, S, Q, w and x
+// (N each), the N-pass's partials (kFsblParts); the R decision records lie side by side and are read by the host in one piece.  norms:
+// the squared column norms, the same for every signal, taken once per call.  b and the pass's partials and control block are the solver
+// slots'.  Apart from FsblBuf: csmp_fsbl's own buffers are neither read nor written.  Made on first use, sized by the dictionary and R:
+// all or none.
+struct FsblBatchBuf {
+    double *Ci = nullptr, *vec = nullptr, *alpha = nullptr, *S = nullptr, *Q = nullptr, *w = nullptr, *x = nullptr, *pval = nullptr,
+           *norms = nullptr;
+    long long* pidx = nullptr;
+    FsblRec* rec = nullptr;
+    int R = 0;          // members the buffers were made for (0: none)
+    int M = 0, Mp = 0;  // ... rows, and the length of each of the two M-vectors in vec
+    int64_t N = 0;      // ... and atoms
+    int64_t ldc = 0;
+};
+
 struct csmp_ctx;
 // Subspace Pursuit as a resumable job: see host/gomp_sp.hpp
 struct SpJob {
@@ -380,6 +397,7 @@ struct csmp_ctx {
     IstaBatchBuf istab;
     SblBuf sbl;
     FsblBuf fsbl;
+    FsblBatchBuf fsblb;
     // profiling
     bool prof = false;
     int prof_every = 1;       // time every n-th sweep launch only (an event pair costs a few us of stream time)

@@ -254,6 +254,7 @@ static int dict_forget(csmp_ctx* ctx) {
     istab_free(ctx->istab);
     sbl_free(ctx->sbl);
     fsbl_free(ctx->fsbl);
+    fsblb_free(ctx->fsblb);
     return CSMP_OK;
 }
 

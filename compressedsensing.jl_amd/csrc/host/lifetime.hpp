@@ -139,6 +139,12 @@ static void fsbl_free(FsblBuf& t) {
     t = FsblBuf();
 }
 
+static void fsblb_free(FsblBatchBuf& t) {
+    dfree(t.Ci); dfree(t.vec); dfree(t.alpha); dfree(t.S); dfree(t.Q); dfree(t.w); dfree(t.x); dfree(t.pval); dfree(t.norms); dfree(t.pidx);
+    dfree(t.rec);
+    t = FsblBatchBuf();
+}
+
 static void dict_release(csmp_ctx* ctx) {
     if (ctx->share && --ctx->share->refs == 0) {
         if (ctx->share->kind == 0) (void)hipFree(ctx->share->p);
@@ -171,6 +177,7 @@ extern "C" int csmp_destroy(csmp_ctx* ctx) {
     istab_free(ctx->istab);
     sbl_free(ctx->sbl);
     fsbl_free(ctx->fsbl);
+    fsblb_free(ctx->fsblb);
     if (ctx->comm) (void)csmp_comm_free(ctx);
     for (auto& t : ctx->twins) {
         if (t) (void)csmp_destroy(t);

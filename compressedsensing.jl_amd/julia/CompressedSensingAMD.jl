@@ -475,6 +475,53 @@ fsbl(A::MatOrDict, b::AbstractVector, Σ::AbstractMatrix; kwargs...) = error("fs
 rmps(A::MatOrDict, b::AbstractVector, Σ::AbstractMatrix; kwargs...) = error("rmps: only a scalar noise variance σ² is served, not a covariance matrix")
 rmps(A::MatOrDict, b::AbstractVector, ::Val{true}, args...; kwargs...) = error("rmps: the σ²-optimising form is not served: pass the noise variance σ²")
 
+# [fsbl(A, B[:, s], σ²_s) for s in axes(B, 2)] and rmps likewise: up to eight signals take their greedy steps in lockstep, the product sweep
+# of a step reads the dictionary once for all of them, every result the single call's bit for bit (csmp_fsbl_batch, csmp_rmps_batch).
+# σ²: one noise variance, or one per signal.  alpha: the N x nsig prior precisions to start from.  return_info: (xs, infos), an info per signal.
+function greedy_batch_setup(A::MatOrDict, B::AbstractMatrix, σ²::Union{Real,AbstractVector}, alpha::Union{Nothing,AbstractMatrix}, cap::Int)
+    D = dict(A)
+    BB = B isa StridedMatrix && eltype(B) <: Union{Float32,Float64} && stride(B, 1) == 1 ? B : convert(Matrix{Float64}, B)
+    size(BB, 1) == size(D, 1) || throw(DimensionMismatch("size(B, 1) = $(size(BB, 1)) but size(A, 1) = $(size(D, 1))"))
+    nsig, N = size(BB, 2), size(D, 2)
+    s2 = σ² isa Real ? Float64[σ²] : convert(Vector{Float64}, σ²)
+    length(s2) in (1, nsig) || throw(DimensionMismatch("length(σ²) = $(length(s2)) but B holds $nsig signals"))
+    α = alpha === nothing ? fill(Inf, N, nsig) : convert(Matrix{Float64}, alpha)
+    size(α) == (N, nsig) || throw(DimensionMismatch("size(alpha) = $(size(α)) but the warm starts are $N x $nsig"))
+    return D, BB, s2, α, zeros(Float64, N, nsig), zeros(Int64, 2, max(cap, 1), max(nsig, 1)), zeros(Int64, nsig), zeros(Cint, nsig)
+end
+greedy_batch_info(it, flags, α, hist, s, n) = (iterations = Int(it[s]), converged = flags[s] & CSMP_FSBL_CONVERGED != 0, alpha = α[:, s],
+                                               history = [(Int(hist[1, t, s]), Int(hist[2, t, s]) + 1) for t in 1:n])
+function fsbl_batch(A::MatOrDict, B::AbstractMatrix, σ²::Union{Real,AbstractVector}; maxiter::Int = 2size(A, 2), min_increase::Real = 1e-6,
+                    alpha::Union{Nothing,AbstractMatrix} = nothing, return_info::Bool = false)
+    cap = max(maxiter, 1)
+    D, BB, s2, α, X, hist, it, flags = greedy_batch_setup(A, B, σ², alpha, cap)
+    nsig, N = size(BB, 2), size(D, 2)
+    GC.@preserve BB s2 α X hist it flags check(D, ccall((:csmp_fsbl_batch, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Ptr{Cdouble}, Int64, Int64, Cdouble, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64,
+         Ptr{Cdouble}, Int64, Cint, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Cint}),
+        D.ctx, BB, dtype_code(eltype(BB)), max(stride(BB, 2), size(BB, 1)), nsig, CSMP_HOST, s2, length(s2), maxiter, min_increase, α, max(N, 1),
+        X, max(N, 1), α, max(N, 1), CSMP_HOST, hist, cap, it, flags))
+    xs = [sparse(X[:, s]) for s in 1:nsig]
+    return return_info ? (xs, [greedy_batch_info(it, flags, α, hist, s, count(!iszero, view(hist, 1, :, s))) for s in 1:nsig]) : xs
+end
+function rmps_batch(A::MatOrDict, B::AbstractMatrix, σ²::Union{Real,AbstractVector}; maxiter::Int = size(A, 1),
+                    maxiter_acquisition::Int = size(A, 1), maxiter_deletion::Int = size(A, 1), min_increase::Real = 1e-6,
+                    alpha::Union{Nothing,AbstractMatrix} = nothing, return_info::Bool = false, history_cap::Int = 4size(A, 2))
+    cap = max(history_cap, 0)
+    D, BB, s2, α, X, hist, it, flags = greedy_batch_setup(A, B, σ², alpha, cap)
+    nsig, N = size(BB, 2), size(D, 2)
+    GC.@preserve BB s2 α X hist it flags check(D, ccall((:csmp_rmps_batch, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Ptr{Cdouble}, Int64, Int64, Int64, Int64, Cdouble, Ptr{Cdouble}, Int64, Ptr{Cdouble},
+         Int64, Ptr{Cdouble}, Int64, Cint, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Cint}),
+        D.ctx, BB, dtype_code(eltype(BB)), max(stride(BB, 2), size(BB, 1)), nsig, CSMP_HOST, s2, length(s2), maxiter, maxiter_acquisition,
+        maxiter_deletion, min_increase, α, max(N, 1), X, max(N, 1), α, max(N, 1), CSMP_HOST, cap == 0 ? C_NULL : pointer(hist), cap, it, flags))
+    xs = [sparse(X[:, s]) for s in 1:nsig]
+    return return_info ? (xs, [greedy_batch_info(it, flags, α, hist, s, min(Int(it[s]), cap)) for s in 1:nsig]) : xs
+end
+fsbl_batch(A::MatOrDict, B::AbstractMatrix, Σ::AbstractMatrix; kwargs...) = error("fsbl_batch: only scalar noise variances σ² are served, not a covariance matrix")
+rmps_batch(A::MatOrDict, B::AbstractMatrix, Σ::AbstractMatrix; kwargs...) = error("rmps_batch: only scalar noise variances σ² are served, not a covariance matrix")
+rmps_batch(A::MatOrDict, B::AbstractMatrix, ::Val{true}, args...; kwargs...) = error("rmps_batch: the σ²-optimising form is not served: pass the noise variance σ²")
+
 # ---------------------------------------------------------------------------------- dictionary analysis
 # src/util.jl:2,96-115: colnorms, coherence, babel, cumbabel.  The inner products are raw, as in the reference (which assumes unit-norm
 # columns); normalize = true divides each by ‖a_i‖ ‖a_j‖.  cumbabel_pair also returns the columns (i, j), i < j, 1-based, that attain

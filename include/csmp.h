@@ -671,6 +671,47 @@ int csmp_rmps(csmp_ctx *ctx, const void *b, int b_dtype, double sigma2, int64_t 
               int64_t maxiter_deletion, double min_increase, const double *alpha_in, double *x, double *alpha_out, int loc,
               int64_t *history, int64_t history_cap, int64_t *iterations, int *flags);
 
+/* fsbl_batch / rmps_batch: csmp_fsbl / csmp_rmps for every column of B in lockstep on shared launches.  The product sweep w = A'v of a
+ * greedy step -- the one read of the dictionary, two thirds of a step at 4096 x 65536 -- is the same read for every signal: a group of up
+ * to eight signals (the groups of csmp_mp_batch and csmp_bp_batch: csmp_tune group_max / group_wide apply) takes its steps together.
+ * One tick of the group is five launches (the N-pass, the decisions, a_i, C^-1 a_i and the rank-one update of every member), ONE read
+ * of all decision records and one shared pass over A for the members that acted; C^-1 stays per signal.  The signals end at different
+ * steps: a slot whose signal is done takes the next unsolved one in ascending order.
+ * Contract: column s of X, column s of alpha_out, iterations[s], flags[s] and signal s's history are those of
+ * csmp_fsbl(ctx, B[:, s], sigma2_s, maxiter, min_increase, alpha_in[:, s], ...) -- of csmp_rmps likewise --, BIT FOR BIT, whatever nsig,
+ * the group sizes and the order the slots are refilled in.
+ * B: size(A,1) x nsig, column-major, leading dimension ldB >= size(A,1), CSMP_F32 or CSMP_F64, on the host or the device (b_loc); read only.
+ * sigma2, nsigma2: a host array of nsigma2 = 1 (one noise variance for every signal) or nsigma2 = nsig (one per signal) values.
+ * X: size(A,2) x nsig doubles, leading dimension ldX >= size(A,2), on the host or the device (x_loc); rows beyond size(A,2) are not
+ * touched.  alpha_in: NULL (every signal starts with all atoms inactive) or size(A,2) x nsig doubles where X lives, leading dimension
+ * ld_alpha_in >= size(A,2), entries positive or +inf; column s is the warm start of signal s.  alpha_out: NULL or size(A,2) x nsig doubles
+ * where X lives, ld_alpha_out >= size(A,2); it may be alpha_in itself (with the same leading dimension).
+ * history (host memory, may be NULL): 2 history_cap nsig words; signal s's pairs (action, index) start at 2 history_cap s and are cut at
+ * history_cap as in the single call.  iterations, flags: host arrays of nsig entries, or NULL.  nsig = 0: CSMP_OK, nothing is touched.
+ * A dictionary without a shared pass (csmp_sweep_config: group 0), CSMP_OPT_SCREENED_SWEEP switched on and nsig = 1 take csmp_fsbl's /
+ * csmp_rmps's own launches signal by signal: the same outputs.
+ * Memory beside csmp_fsbl's, kept by the context until csmp_set_dictionary: per member of a group C^-1, size(A,1)^2 doubles, and five
+ * vectors of size(A,2) doubles -- 1 GiB + 20 MiB for eight members at 4096 x 65536.
+ * CSMP_EINVAL: nsig < 0, null pointers, a dtype / location that is neither, nsigma2 other than 1 or nsig, a sigma2 that is not positive
+ * and finite, min_increase negative or NaN, a cap < 1, history_cap < 0, an entry of alpha_in that is not positive (or NaN) -- and, during
+ * the run, a value of the marginal likelihood's change that is not finite (the message names the signal).  CSMP_EDIM: ldB < size(A,1);
+ * ldX, ld_alpha_in or ld_alpha_out < size(A,2).  CSMP_ESTATE: no dictionary, or a host-streamed one.  CSMP_ERANGE: more than 2^19 rows.
+ * CSMP_ENOMEM: the members' buffers, R x size(A,1)^2 doubles and the vectors, could not be allocated; none of them is left behind and the
+ * context stays usable.  R is the group's size (eight where wide groups are on and nsig exceeds a narrow group, else up to four): the
+ * call does NOT fall back to fewer members -- where R matrices do not fit beside the dictionary, the loop over csmp_fsbl / csmp_rmps,
+ * which keeps one, is the caller's way.  Everything is validated before any device work.  A refused call writes nothing. */
+int csmp_fsbl_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc,
+                    const double *sigma2, int64_t nsigma2, int64_t maxiter, double min_increase,
+                    const double *alpha_in, int64_t ld_alpha_in, double *X, int64_t ldX,
+                    double *alpha_out, int64_t ld_alpha_out, int x_loc,
+                    int64_t *history, int64_t history_cap, int64_t *iterations, int *flags);
+int csmp_rmps_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc,
+                    const double *sigma2, int64_t nsigma2, int64_t maxiter, int64_t maxiter_acquisition,
+                    int64_t maxiter_deletion, double min_increase,
+                    const double *alpha_in, int64_t ld_alpha_in, double *X, int64_t ldX,
+                    double *alpha_out, int64_t ld_alpha_out, int x_loc,
+                    int64_t *history, int64_t history_cap, int64_t *iterations, int *flags);
+
 /* ------------------------------------------------------------------ dictionary analysis
  * colnorms(A): src/util.jl:2.  norms[j] = ||a_j||_2 of every column of the resident dictionary, N doubles, to host memory
  * (out_loc = CSMP_HOST) or device memory (CSMP_DEVICE; the call still returns with the work done).  Float64 on the exactly
