@@ -107,6 +107,8 @@ SIGNATURES = {
                                   C.POINTER(i64), C.POINTER(C.c_int)]),
     "csmp_rmps_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, vp, i64, i64, i64, i64, C.c_double, vp, i64, vp, i64, vp, i64, C.c_int, vp,
                                   i64, C.POINTER(i64), C.POINTER(C.c_int)]),
+    "csmp_ompr_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, i64, C.POINTER(C.c_double), i64, i64, vp, vp, vp, C.POINTER(i64),
+                                  C.POINTER(C.c_int)]),
     "csmp_colnorms": (C.c_int, [vp, vp, C.c_int]),
     "csmp_cumbabel": (C.c_int, [vp, i64, C.c_int, vp, vp]),
     "csmp_sweep": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -148,6 +150,7 @@ BPD_CONVERGED, BPD_FACTORED = 1, 2  # CSMP_BPD_*
 BPD_RHO = 100.0  # the bindings' default penalty of bpd
 SBL_CONVERGED = 1  # CSMP_SBL_*
 FSBL_CONVERGED = RMPS_CONVERGED = 1  # CSMP_FSBL_*, CSMP_RMPS_*
+OMPR_SOLVED_ALONE = 1  # CSMP_OMPR_SOLVED_ALONE
 FSBL_MODES = {"all": 1, "add": 2, "rmp_delete": 3, "update": 4}  # csmp_fsbl_score's modes
 
 
@@ -413,6 +416,44 @@ class Context:
                   ptr(idx), ptr(val), C.byref(nnz), C.byref(iters))
         n = nnz.value
         return idx[:n].copy(), val[:n].copy(), iters.value
+
+    def _ompr_batch_call(self, B, code, ldB, nsig, b_loc, k, delta, maxiter):
+        """csmp_ompr_batch: the outputs live on the host whatever b_loc is -> (idx k x nsig, val, nnz, info)"""
+        d = np.ascontiguousarray(np.atleast_1d(np.asarray(delta, dtype=np.float64)))
+        if d.ndim != 1:
+            raise CsmpError(EDIM, "delta has to be a scalar or one value per signal")
+        kk = max(int(k), 1)
+        idx = np.zeros((kk, max(nsig, 1)), np.int64, order="F")
+        val = np.zeros((kk, max(nsig, 1)), np.float64, order="F")
+        nnz, it, fl = np.zeros(max(nsig, 1), np.int64), np.zeros(max(nsig, 1), np.int64), np.zeros(max(nsig, 1), np.int32)
+        self.call("csmp_ompr_batch", B, code, i64(ldB), i64(nsig), b_loc, i64(int(k)), d.ctypes.data_as(C.POINTER(C.c_double)), i64(len(d)),
+                  i64(-1 if maxiter is None else int(maxiter)), ptr(idx), ptr(val), ptr(nnz), it.ctypes.data_as(C.POINTER(i64)),
+                  fl.ctypes.data_as(C.POINTER(C.c_int)))
+        info = {"iterations": it[:nsig], "solved_alone": (fl[:nsig] & OMPR_SOLVED_ALONE) != 0}
+        return idx[:, :nsig], val[:, :nsig], nnz[:nsig], info
+
+    def ompr_batch(self, B, k, delta, maxiter=None):
+        """csmp_ompr_batch on the host matrix B (M x nsig): ompr for every column, the update!s of a group's signals in lockstep on shared
+        launches -> (idx k x nsig, val, nnz, info = iterations int64[nsig], solved_alone bool[nsig]).  Column s is ompr(B[:, s], k,
+        delta_s, maxiter)'s bit for bit.  delta: a scalar or one value per signal; maxiter=None: size(A, 1)."""
+        B = np.asfortranarray(B)
+        if B.dtype not in (np.float32, np.float64):
+            B = B.astype(np.float64)
+        if B.ndim != 2 or B.shape[0] != self.M:
+            raise CsmpError(EDIM, f"size(B) = {B.shape} but size(A, 1) = {self.M}")
+        return self._ompr_batch_call(ptr(B), dtype_code(B.dtype), max(self.M, 1), B.shape[1], HOST, k, delta, maxiter)
+
+    def ompr_batch_device(self, B, k, delta, maxiter=None):
+        """as ompr_batch, on a torch CUDA matrix whose COLUMNS are the signals: B (M, nsig) float32 / float64 with stride (1, ldB >= M).
+        The results come back as ompr_batch's host arrays; the work is done when the call returns."""
+        import torch
+        if not (B.is_cuda and B.dim() == 2 and B.shape[0] == self.M and B.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "B must be a CUDA matrix of size(A, 1) rows, float32 or float64")
+        nsig = B.shape[1]
+        ldB = B.stride(1) if nsig > 1 else max(self.M, 1)
+        if (self.M > 1 and B.stride(0) != 1) or ldB < self.M:
+            raise CsmpError(EDIM, "B must be column-major: unit row stride, a column stride of at least its row count")
+        return self._ompr_batch_call(vp(B.data_ptr()), F32 if B.dtype == torch.float32 else F64, ldB, nsig, DEVICE, k, delta, maxiter)
 
     def fr(self, b, k, max_eps=0.0, min_delta=0.0):
         b = self._b(b)

@@ -772,6 +772,35 @@ def ompr(A, b, k, delta, maxiter=None):
             D.close()
 
 
+def ompr_batch(A, B, k, delta, maxiter=None, return_info=False):
+    """[ompr(A, B[:, s], k, delta_s; maxiter) for s in axes(B, 2)] on one GPU: up to eight signals take their update! in lockstep, so the
+    product sweep of an iteration reads the dictionary once for all of them (include/csmp.h, csmp_ompr_batch).  Every result is ompr's
+    bit for bit.  delta: one threshold, or one per column.  Returns a list of SparseVectors; return_info=True: (xs, info) with the
+    per-signal iterations and solved_alone (the signal left its group and was solved by the single path)."""
+    M, N, _ = _meta(A)
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] != M:
+        raise ValueError(f"size(B) = {B.shape} but size(A, 1) = {M}: B holds one signal per column")
+    nsig = B.shape[1]
+    if not _is_int(k) or not 1 <= k <= min(M, N):
+        raise ValueError(f"k = {k} has to lie in 1 .. min(size(A)) = {min(M, N)}")
+    d = np.asarray(delta, dtype=np.float64)
+    if d.ndim > 1 or (d.ndim == 1 and d.shape[0] != nsig):
+        raise ValueError(f"delta has to be a scalar or one value per signal: size(delta) = {d.shape} but B holds {nsig} signals")
+    if np.any(np.isnan(d)):
+        raise ValueError(f"delta = {delta} is NaN")
+    if maxiter is not None and (not _is_int(maxiter) or maxiter < 0):
+        raise ValueError(f"maxiter = {maxiter} has to be a non-negative integer")
+    D, tmp = _dict(A)
+    try:
+        idx, val, nnz, info = D.ctx.ompr_batch(B, int(k), d, maxiter)
+        xs = [SparseVector(N, idx[:nnz[s], s].copy(), val[:nnz[s], s].copy()) for s in range(nsig)]
+        return (xs, info) if return_info else xs
+    finally:
+        if tmp:
+            D.close()
+
+
 def fr(A, b, *args, max_residual=0.0, min_decrease=0.0, sparsity=None):
     """fr(A,b,max_eps,min_delta,k=size(A,1)) and fr(A,b; max_residual=0, min_decrease=0, sparsity=size(A,2)):
     forward regression / orthogonal least squares (src/forward.jl:34-54), x starting empty."""

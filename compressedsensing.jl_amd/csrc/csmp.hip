@@ -54,6 +54,7 @@ using namespace csmp;
 #include "host/removal.hpp"
 #include "host/gomp_sp.hpp"
 #include "host/twostage.hpp"
+#include "host/ompr_batch.hpp"
 #include "host/steps_twostage.hpp"
 #include "host/batched.hpp"
 #include "host/screened.hpp"

@@ -35,10 +35,12 @@ __global__ __launch_bounds__(256) void k_swap_init(const double* __restrict__ T,
 
 // One wave per slot: out[j] = <a_sel[j], v> for the k slots (v = the joining atom's column, or b for the right-hand side
 // c = A_S'b); with TV == TA two more waves: out[k] = <v, v> and out[k + 1] = <v, b>.  Float64 products of the promoted values.
+// (the bodies of the chain's kernels are __device__ functions: the single kernels run them on the active slot, the group kernels at
+// the end of this file on every member of a lockstep group -- csmp_ompr_batch -- with the member's own pointers: the same arithmetic)
 template <typename TA, typename TV>
-__global__ __launch_bounds__(256) void k_swap_dots(const TA* __restrict__ A, int64_t ld, int M, const int* __restrict__ sel, int k,
-                                                   const TV* __restrict__ v, const double* __restrict__ b, int extras,
-                                                   double* __restrict__ out, const int* __restrict__ meta) {
+__device__ __forceinline__ void swap_dots_body(const TA* __restrict__ A, int64_t ld, int M, const int* __restrict__ sel, int k,
+                                               const TV* __restrict__ v, const double* __restrict__ b, int extras,
+                                               double* __restrict__ out, const int* __restrict__ meta) {
     const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (j >= k + extras) return;
     if (meta) {  // (v: the joining atom's column)
@@ -98,6 +100,12 @@ __global__ __launch_bounds__(256) void k_swap_dots(const TA* __restrict__ A, int
     acc = wave_xsum(acc);
     if (lane == 0) out[j] = acc;
 }
+template <typename TA, typename TV>
+__global__ __launch_bounds__(256) void k_swap_dots(const TA* __restrict__ A, int64_t ld, int M, const int* __restrict__ sel, int k,
+                                                   const TV* __restrict__ v, const double* __restrict__ b, int extras,
+                                                   double* __restrict__ out, const int* __restrict__ meta) {
+    swap_dots_body<TA, TV>(A, ld, M, sel, k, v, b, extras, out, meta);
+}
 
 // u = H' g, then everything that hangs on it, in ONE launch of nch workgroups.  Workgroup cb: the partial sums of u over the
 // kSwapChunk columns of chunk cb for every row (H'_rj = H_rj - H_rp H_pj / H_pp, row p and column p excluded).  The workgroup that
@@ -105,12 +113,12 @@ __global__ __launch_bounds__(256) void k_swap_dots(const TA* __restrict__ A, int
 // sigma and the guard, the coefficient updates, the slot's new owner, column p of the old H saved for the commit, and x emitted
 // in index order (the list the next k_ompr_pick gathers with).
 // info[0] = sigma, info[1] = H_pp (old), info[2] = 1 when the exchange was refused (nothing changed).
-__global__ __launch_bounds__(256) void k_swap_ufin(const double* __restrict__ H, int ldh, int k, const int* __restrict__ meta,
-                                                   const double* __restrict__ g, double* __restrict__ part, int nch,
-                                                   unsigned* __restrict__ counter, double* __restrict__ u, double* __restrict__ x,
-                                                   double* __restrict__ c, int* __restrict__ sel, double* __restrict__ hp,
-                                                   double* __restrict__ info, int64_t* __restrict__ out_idx, double* __restrict__ out_val,
-                                                   int64_t* __restrict__ out_nnz, double guard) {
+__device__ __forceinline__ void swap_ufin_body(const double* __restrict__ H, int ldh, int k, const int* __restrict__ meta,
+                                               const double* __restrict__ g, double* __restrict__ part, int nch,
+                                               unsigned* __restrict__ counter, double* __restrict__ u, double* __restrict__ x,
+                                               double* __restrict__ c, int* __restrict__ sel, double* __restrict__ hp,
+                                               double* __restrict__ info, int64_t* __restrict__ out_idx, double* __restrict__ out_val,
+                                               int64_t* __restrict__ out_nnz, double guard) {
     __shared__ double red[8];
     __shared__ double sh_xa;
     __shared__ int last;
@@ -195,16 +203,24 @@ __global__ __launch_bounds__(256) void k_swap_ufin(const double* __restrict__ H,
         out_val[rank] = x[t];
     }
 }
+__global__ __launch_bounds__(256) void k_swap_ufin(const double* __restrict__ H, int ldh, int k, const int* __restrict__ meta,
+                                                   const double* __restrict__ g, double* __restrict__ part, int nch,
+                                                   unsigned* __restrict__ counter, double* __restrict__ u, double* __restrict__ x,
+                                                   double* __restrict__ c, int* __restrict__ sel, double* __restrict__ hp,
+                                                   double* __restrict__ info, int64_t* __restrict__ out_idx, double* __restrict__ out_val,
+                                                   int64_t* __restrict__ out_nnz, double guard) {
+    swap_ufin_body(H, ldh, k, meta, g, part, nch, counter, u, x, c, sel, hp, info, out_idx, out_val, out_nnz, guard);
+}
 
 // One launch for the two things that follow and do not depend on each other.  Workgroups [0, ncommit): the new H, entry by entry
 // (no dependent chain: u, the saved column hp and sigma are complete).  The others: k_residual_part's share (row block, chunk) of
 // A_S x for the new coefficients.
 template <typename TA>
-__global__ __launch_bounds__(256) void k_swap_commit_res(double* __restrict__ H, int ldh, int k, const int* __restrict__ meta,
-                                                         const double* __restrict__ u, const double* __restrict__ hp,
-                                                         const double* __restrict__ info, int ncommit, const TA* __restrict__ A,
-                                                         int64_t ld, int M, const int* __restrict__ sel, const double* __restrict__ x,
-                                                         int nrb, double* __restrict__ rpart) {
+__device__ __forceinline__ void swap_commit_res_body(double* __restrict__ H, int ldh, int k, const int* __restrict__ meta,
+                                                     const double* __restrict__ u, const double* __restrict__ hp,
+                                                     const double* __restrict__ info, int ncommit, const TA* __restrict__ A,
+                                                     int64_t ld, int M, const int* __restrict__ sel, const double* __restrict__ x,
+                                                     int nrb, double* __restrict__ rpart) {
     if (meta[0] != 1 || info[2] != 0.0) return;
     if ((int)blockIdx.x < ncommit) {
         const int p = meta[3];
@@ -239,11 +255,19 @@ __global__ __launch_bounds__(256) void k_swap_commit_res(double* __restrict__ H,
     for (; t < t1; ++t) a0 = fma((double)A[(int64_t)sel[t] * ld + row], x[t], a0);
     rpart[(int64_t)ch * M + row] = a0 + a1;
 }
+template <typename TA>
+__global__ __launch_bounds__(256) void k_swap_commit_res(double* __restrict__ H, int ldh, int k, const int* __restrict__ meta,
+                                                         const double* __restrict__ u, const double* __restrict__ hp,
+                                                         const double* __restrict__ info, int ncommit, const TA* __restrict__ A,
+                                                         int64_t ld, int M, const int* __restrict__ sel, const double* __restrict__ x,
+                                                         int nrb, double* __restrict__ rpart) {
+    swap_commit_res_body<TA>(H, ldh, k, meta, u, hp, info, ncommit, A, ld, M, sel, x, nrb, rpart);
+}
 
 // r = b - (chunk sums of the residual shares), and the workgroup's share of |r|^2 (the host adds the shares in order)
-__global__ __launch_bounds__(256) void k_swap_rsum(const double* __restrict__ part, int nch, int M, const double* __restrict__ b,
-                                                   double* __restrict__ r, const double* __restrict__ info, double* __restrict__ n2part,
-                                                   const int* __restrict__ meta) {
+__device__ __forceinline__ void swap_rsum_body(const double* __restrict__ part, int nch, int M, const double* __restrict__ b,
+                                               double* __restrict__ r, const double* __restrict__ info, double* __restrict__ n2part,
+                                               const int* __restrict__ meta) {
     __shared__ double red[8];
     if (meta[0] != 1 || info[2] != 0.0) return;
     const int row = blockIdx.x * 256 + threadIdx.x;
@@ -256,6 +280,73 @@ __global__ __launch_bounds__(256) void k_swap_rsum(const double* __restrict__ pa
     }
     v = block_sum256(v * v, red);
     if (threadIdx.x == 0) n2part[blockIdx.x] = v;
+}
+__global__ __launch_bounds__(256) void k_swap_rsum(const double* __restrict__ part, int nch, int M, const double* __restrict__ b,
+                                                   double* __restrict__ r, const double* __restrict__ info, double* __restrict__ n2part,
+                                                   const int* __restrict__ meta) {
+    swap_rsum_body(part, nch, M, b, r, info, n2part, meta);
+}
+
+// ------------------------------------------------------------------------------------------ the chain for a lockstep group
+// csmp_ompr_batch (host/ompr_batch.hpp): ONE launch of each kernel of the chain for all members of a group (OmprGroup, csmp_tinv.hpp;
+// grid z = the member), behind k_ompr_pick_group.  Every member runs the single kernel's body on its own slot and exchange buffers --
+// the same workgroup shape, the same order of every sum -- so its numbers are the single chain's bit for bit; a member whose
+// meta[0] != 1 leaves every kernel at once, as in the single chain.  k_swap_ufin's last-workgroup counter is the member's own.
+template <typename TA>
+__global__ __launch_bounds__(256) void k_swap_dots_group(const TA* __restrict__ A, int64_t ld, int M, OmprGroup G) {
+    const int m = blockIdx.z;
+    swap_dots_body<TA, TA>(A, ld, M, G.sel[m], G.k, A, G.b[m], 2, G.g[m], G.meta[m]);
+}
+__global__ __launch_bounds__(256) void k_swap_ufin_group(OmprGroup G, int nch, double guard) {
+    const int m = blockIdx.z;
+    swap_ufin_body(G.H[m], G.ldh[m], G.k, G.meta[m], G.g[m], G.upart[m], nch, G.counter[m], G.u[m], G.x[m], G.c[m], G.sel[m], G.hp[m], G.info[m],
+                   G.out_idx[m], G.out_val[m], G.out_nnz[m], guard);
+}
+template <typename TA>
+__global__ __launch_bounds__(256) void k_swap_commit_res_group(const TA* __restrict__ A, int64_t ld, int M, OmprGroup G, int ncommit, int nrb) {
+    const int m = blockIdx.z;
+    swap_commit_res_body<TA>(G.H[m], G.ldh[m], G.k, G.meta[m], G.u[m], G.hp[m], G.info[m], ncommit, A, ld, M, G.sel[m], G.x[m], nrb, G.rpart[m]);
+}
+__global__ __launch_bounds__(256) void k_swap_rsum_group(OmprGroup G, int nch, int M) {
+    const int m = blockIdx.z;
+    swap_rsum_body(G.rpart[m], nch, M, G.b[m], G.r[m], G.info[m], G.n2[m], G.meta[m]);
+}
+// What the host reads after a tick, for all members in one launch: member m's landing -- the sorted support and its values (k each),
+// the nshare shares of |r|^2, info (4 doubles), meta (4 ints) and the control block -- as consecutive 8-byte words from word m * stride
+// of `land`, page-locked host memory (k_land_multi's scheme; every piece is whole, 8-byte aligned words).
+constexpr int kSwapLandStWords = (int)(sizeof(DevState) / 8);
+static_assert(sizeof(DevState) % 8 == 0, "the control block lands as whole 8-byte words");
+__host__ __device__ inline int swap_land_words(int k, int nshare) { return 2 * k + nshare + 4 + 2 + kSwapLandStWords; }
+__global__ __launch_bounds__(256) void k_swap_land_group(OmprGroup G, int nshare, int stride, unsigned long long* __restrict__ land) {
+    using W = unsigned long long;
+    const int m = blockIdx.z, k = G.k;
+    const int words = swap_land_words(k, nshare);
+    W* dst = land + (size_t)m * stride;
+    for (int w = blockIdx.x * 256 + threadIdx.x; w < words; w += gridDim.x * 256) {
+        int o = w;
+        const W* p = reinterpret_cast<const W*>(G.out_idx[m]);
+        if (o >= k) {
+            o -= k;
+            p = reinterpret_cast<const W*>(G.out_val[m]);
+            if (o >= k) {
+                o -= k;
+                p = reinterpret_cast<const W*>(G.n2[m]);
+                if (o >= nshare) {
+                    o -= nshare;
+                    p = reinterpret_cast<const W*>(G.info[m]);
+                    if (o >= 4) {
+                        o -= 4;
+                        p = reinterpret_cast<const W*>(G.meta[m]);
+                        if (o >= 2) {
+                            o -= 2;
+                            p = reinterpret_cast<const W*>(G.st[m]);
+                        }
+                    }
+                }
+            }
+        }
+        dst[w] = p[o];
+    }
 }
 
 }  // namespace csmp

@@ -242,10 +242,11 @@ __global__ __launch_bounds__(256) void k_emit_sorted(const double* __restrict__ 
 // OMPR's update!, between the sweep and the host's decision (one workgroup): the arg-max over the sweep's partials (k_select, mode 0:
 // no guards) and c[i] for the atoms of the support in INDEX order (the sorted list the last k_emit_sorted left on the device) --
 // the numbers "x.nzval = P.Ar[x.nzind]" needs (src/twostage.jl:166).  It was three launches: the support going up, k_select, k_gather.
-__global__ __launch_bounds__(256) void k_ompr_pick(const double* __restrict__ pval, const int* __restrict__ pidx, int nblk,
-                                                   const double* __restrict__ cvec, DevState* st, const int64_t* __restrict__ sorted_idx,
-                                                   int k, double* __restrict__ cs, const double* __restrict__ sorted_val,
-                                                   const int* __restrict__ sel, int* __restrict__ meta) {
+// (the body: k_ompr_pick runs it on the active slot, k_ompr_pick_group on every member of a lockstep group)
+__device__ __forceinline__ void ompr_pick_body(const double* __restrict__ pval, const int* __restrict__ pidx, int nblk,
+                                               const double* __restrict__ cvec, DevState* st, const int64_t* __restrict__ sorted_idx,
+                                               int k, double* __restrict__ cs, const double* __restrict__ sorted_val,
+                                               const int* __restrict__ sel, int* __restrict__ meta) {
     __shared__ double sv[256];
     __shared__ int si[256];
     __shared__ int cnt[2];
@@ -321,6 +322,45 @@ __global__ __launch_bounds__(256) void k_ompr_pick(const double* __restrict__ pv
         meta[1] = leaving;
         meta[2] = bi;
     }
+}
+__global__ __launch_bounds__(256) void k_ompr_pick(const double* __restrict__ pval, const int* __restrict__ pidx, int nblk,
+                                                   const double* __restrict__ cvec, DevState* st, const int64_t* __restrict__ sorted_idx,
+                                                   int k, double* __restrict__ cs, const double* __restrict__ sorted_val,
+                                                   const int* __restrict__ sel, int* __restrict__ meta) {
+    ompr_pick_body(pval, pidx, nblk, cvec, st, sorted_idx, k, cs, sorted_val, sel, meta);
+}
+
+// csmp_ompr_batch (host/ompr_batch.hpp): the members of a lockstep group, passed by value.  Member i's update! runs on its own solver
+// slot (the pass's partials and c, the control block, the sorted support, x in slot order, b, r) and on that slot's exchange buffers
+// (csmp_swap.hpp: H, g, the partials of u, u, the saved column, c on the support, info, the residual shares, meta, the counter).
+constexpr int kOmprGroupMax = kWideMax;
+struct OmprGroup {
+    int n;     // members
+    int k;     // atoms of every member's support
+    int nblk;  // arg-max partials the tick's pass left per member
+    const double* pval[kOmprGroupMax];
+    const int* pidx[kOmprGroupMax];
+    const double* cvec[kOmprGroupMax];
+    DevState* st[kOmprGroupMax];
+    int64_t* out_idx[kOmprGroupMax];
+    double* out_val[kOmprGroupMax];
+    int64_t* out_nnz[kOmprGroupMax];
+    double* coef[kOmprGroupMax];
+    int* sel[kOmprGroupMax];
+    double* x[kOmprGroupMax];
+    const double* b[kOmprGroupMax];
+    double* r[kOmprGroupMax];
+    double* H[kOmprGroupMax];
+    int ldh[kOmprGroupMax];
+    double *g[kOmprGroupMax], *upart[kOmprGroupMax], *u[kOmprGroupMax], *hp[kOmprGroupMax], *c[kOmprGroupMax], *info[kOmprGroupMax];
+    double *rpart[kOmprGroupMax], *n2[kOmprGroupMax];
+    int* meta[kOmprGroupMax];
+    unsigned* counter[kOmprGroupMax];
+};
+// k_ompr_pick for every member (grid z): the arg-max over the partials of ITS stream of the pass, the decision into its meta
+__global__ __launch_bounds__(256) void k_ompr_pick_group(OmprGroup G) {
+    const int m = blockIdx.z;
+    ompr_pick_body(G.pval[m], G.pidx[m], G.nblk, G.cvec[m], G.st[m], G.out_idx[m], G.k, G.coef[m], G.out_val[m], G.sel[m], G.meta[m]);
 }
 // ... and after it: the atom that leaves -> its insertion position (k_find_pos), the atom that joins -> the append's candidate list
 __global__ __launch_bounds__(256) void k_swap_prep(const int* __restrict__ sel, const DevState* st, int leaving, int joining,

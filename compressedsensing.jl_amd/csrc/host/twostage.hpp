@@ -24,8 +24,8 @@ struct OmprJob {
     int nchk = 0, nchm = 0, nshare = 0;
 
     // H = (A_S'A_S)^-1 = T T' from the explicit inverse factor the acquisition built, c = A_S'b, x in slot order (s.bwd_coef)
-    template <typename TA>
-    int gram_begin_t() {
+    // the active slot's exchange buffers for supports of k atoms (made on first use; csmp_ompr_batch makes every member's up front)
+    int gram_ensure() {
         Solver& s = ctx->s;
         const int kk = (int)k, M = (int)ctx->M;
         nchk = (kk + kSwapChunk - 1) / kSwapChunk;
@@ -35,9 +35,17 @@ struct OmprJob {
         if (!s.swapH) CHECK(dmalloc(ctx, &s.swapH, (size_t)s.kcap * s.kcap));
         if (s.swapv_cap < need) {
             dfree(s.swapv);
+            s.swapv_cap = 0;
             CHECK(dmalloc(ctx, &s.swapv, need));
             s.swapv_cap = need;
         }
+        return CSMP_OK;
+    }
+    template <typename TA>
+    int gram_begin_t() {
+        Solver& s = ctx->s;
+        const int kk = (int)k, M = (int)ctx->M;
+        CHECK(gram_ensure());
         dG = s.swapv;
         dUpart = dG + kk + 2;
         dU = dUpart + (size_t)nchk * kk;
@@ -159,7 +167,8 @@ struct OmprJob {
     }
 
     // OMPR(A, b, k) (:124-132): buffers, b on the device, empty support, r = b
-    int begin(csmp_ctx* c, const void* b, int b_dtype, int64_t kk) {
+    // the active slot's buffers for a solve with k atoms
+    int prepare(csmp_ctx* c, int64_t kk) {
         ctx = c;
         k = kk;
         use_downdate = k <= kTMaxCols;  // (beyond: refactorise instead)
@@ -169,6 +178,21 @@ struct OmprJob {
         ctx->s.begun = false;
         if (use_downdate) CHECK(del_ensure(ctx));
         if (tmode) CHECK(tinv_ensure(ctx));
+        return CSMP_OK;
+    }
+    // ... and the empty support (csmp_ompr_batch: b is in the slot already, the sweeps are exact)
+    void reset() {
+        screened = false;
+        xi.clear();
+        xv.clear();
+        cs.assign((size_t)k, 0.0);
+        unc_seen = 0;
+        resnorm = 0.0;
+        gram = false;
+        gram_exchanges = 0;
+    }
+    int begin(csmp_ctx* c, const void* b, int b_dtype, int64_t kk) {
+        CHECK(prepare(c, kk));
         CHECK(upload_b(ctx, b, b_dtype));
         // CSMP_OPT_SCREENED_SWEEP: the sweeps read the image; the oblivious acquisition's top-k set and every update!'s arg-max are
         // certified (host/screened.hpp), the correlations on the support are computed exactly beside them; a sweep whose
@@ -207,6 +231,10 @@ struct OmprJob {
             ctx->scr_fallbacks += 1;
             scr = false;
         }
+        return acquire_fit(top);
+    }
+    // ... from the selected atoms on: least squares on them, the explicit inverse, the inverse Gram matrix, ||r||
+    int acquire_fit(std::vector<int>& top) {
         std::sort(top.begin(), top.end());
         CHECK(ls_on_columns(ctx, top));
         if (tmode) {

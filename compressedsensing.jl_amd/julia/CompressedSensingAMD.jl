@@ -573,6 +573,29 @@ function ompr(A::MatOrDict{T}, b::AbstractVector, k::Int, δ::Real; maxiter = si
     to_sparse(size(D, 2), idx, val, nnz[])
 end
 
+# [ompr(A, B[:, s], k, δ_s; maxiter) for s in axes(B, 2)]: up to eight signals take their update! in lockstep, the product sweep of an
+# iteration reads the dictionary once for all of them, every result the single call's bit for bit (csmp_ompr_batch).  δ: one threshold,
+# or one per column.  return_info: (xs, infos), per signal the iterations and whether it was solved alone (it left its group).
+const CSMP_OMPR_SOLVED_ALONE = 1
+function ompr_batch(A::MatOrDict, B::AbstractMatrix, k::Int, δ::Union{Real,AbstractVector}; maxiter::Int = size(A, 1), return_info::Bool = false)
+    D = dict(A)
+    BB = B isa StridedMatrix && eltype(B) <: Union{Float32,Float64} && stride(B, 1) == 1 ? B : convert(Matrix{Float64}, B)
+    size(BB, 1) == size(D, 1) || throw(DimensionMismatch("size(B, 1) = $(size(BB, 1)) but size(A, 1) = $(size(D, 1))"))
+    nsig = size(BB, 2)
+    1 <= k <= min(size(D, 1), size(D, 2)) || throw(ArgumentError("k = $k has to lie in 1:min(size(A)...)"))
+    d = δ isa Real ? Float64[δ] : convert(Vector{Float64}, δ)
+    length(d) in (1, nsig) || throw(DimensionMismatch("length(δ) = $(length(d)) but B holds $nsig signals"))
+    any(isnan, d) && throw(ArgumentError("δ is NaN"))
+    idx, val = zeros(Int64, k, max(nsig, 1)), zeros(Float64, k, max(nsig, 1))
+    nnz, it, flags = zeros(Int64, max(nsig, 1)), zeros(Int64, max(nsig, 1)), zeros(Cint, max(nsig, 1))
+    GC.@preserve BB d idx val nnz it flags check(D, ccall((:csmp_ompr_batch, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Int64, Ptr{Cdouble}, Int64, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int64},
+         Ptr{Cint}),
+        D.ctx, BB, dtype_code(eltype(BB)), max(stride(BB, 2), size(BB, 1)), nsig, CSMP_HOST, k, d, length(d), maxiter, idx, val, nnz, it, flags))
+    xs = [to_sparse(size(D, 2), idx[:, s], val[:, s], nnz[s]) for s in 1:nsig]
+    return return_info ? (xs, [(iterations = Int(it[s]), solved_alone = flags[s] & CSMP_OMPR_SOLVED_ALONE != 0) for s in 1:nsig]) : xs
+end
+
 # ---------------------------------------------------------------------------------- fr = ols = oomp = ormp
 # src/forward.jl:34-54 (x starting empty)
 function fr(A::MatOrDict{T}, b::AbstractVector, max_ε::Real, min_δ::Real, k::Int = size(A, 1)) where {T}

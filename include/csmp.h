@@ -132,6 +132,26 @@ int csmp_sp(csmp_ctx *ctx, const void *b, int b_dtype, int64_t k, double delta, 
 int csmp_ompr(csmp_ctx *ctx, const void *b, int b_dtype, int64_t k, double delta, int64_t maxiter, int64_t *idx,
               double *val, int64_t *nnz, int64_t *iters);
 
+/* ompr_batch: csmp_ompr(ctx, B[:, s], k, delta_s, maxiter) for every column of B, the update!s of up to sweep_group signals -- group_wide
+ * where wide groups are granted -- in lockstep: ONE shared pass reads the dictionary for all members of a group, one launch of each
+ * kernel of the exchange chain serves all of them, and the host reads one landing per tick (host/ompr_batch.hpp).
+ * Every result is the single call's bit for bit -- support, coefficients, iteration count -- whatever the batch size, the group
+ * size and the order in which freed slots are refilled.
+ * B: ldB x nsig, column-major, host or device memory (b_loc); idx, val: k x nsig, nnz, iters: nsig, HOST memory (csmp_omp_batch's
+ * layout: signal s's entries from s * k, nnz[s] of them written); iters and flags may be NULL.  delta: ndelta = 1 threshold for all
+ * signals or ndelta = nsig, one per column.  maxiter < 0 selects size(A,1), as csmp_ompr.
+ * flags[s]: CSMP_OMPR_SOLVED_ALONE -- the signal left its group (an exchange the guard refused, an arg-max inside the support, an
+ * acquisition short of k atoms: the steps off the inverse Gram matrix's fast path) and was solved from the start by csmp_ompr.
+ * The whole call is the loop over csmp_ompr where the dictionary has no shared pass (or csmp_tune switched it off), for nsig < 2, with
+ * CSMP_OPT_SCREENED_SWEEP on, on a host-streamed dictionary and for k > 4095: the same results.
+ * CSMP_EINVAL: NULL arguments, k < 1, nsig < 0, ndelta neither 1 nor nsig, a NaN delta, a bad b_dtype or b_loc.  CSMP_EDIM: ldB <
+ * size(A,1).  CSMP_ERANGE: k > min(size(A)).  CSMP_ESTATE: no dictionary.  CSMP_ENOMEM: a member's buffers could not be allocated;
+ * the context and the library stay usable.  nsig == 0: CSMP_OK, the device is not touched. */
+#define CSMP_OMPR_SOLVED_ALONE 1
+int csmp_ompr_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k,
+                    const double *delta, int64_t ndelta, int64_t maxiter,
+                    int64_t *idx, double *val, int64_t *nnz, int64_t *iters, int *flags);
+
 /* fr(A,b,max_eps,min_delta,k) = ols = oomp = ormp: forward regression / orthogonal least squares,
  * src/forward.jl:44-54 (forward_step! :56-73, forward_δ! :75-82, ols_rescaling! :99-114), with x
  * starting empty.  Each step adds the atom maximising <a_j,r>^2 / (|a_j|^2 - |Q_S' a_j|^2); stops
