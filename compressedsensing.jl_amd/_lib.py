@@ -66,6 +66,8 @@ SIGNATURES = {
     "csmp_br": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_double, i64, C.c_int, vp, vp, C.POINTER(i64)]),
     "csmp_fr_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, i64, C.c_double, C.c_double, vp, vp, vp, C.c_int]),
     "csmp_mp_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, i64, vp, vp, vp, C.c_int]),
+    "csmp_somp": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, i64, C.c_double, C.c_int, vp, vp, i64, C.POINTER(i64), vp, vp, C.POINTER(i64),
+                            C.c_int]),
     "csmp_ompr": (C.c_int, [vp, vp, C.c_int, i64, C.c_double, i64, vp, vp, C.POINTER(i64), C.POINTER(i64)]),
     "csmp_omp_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, i64, C.c_double, vp, vp, vp, C.c_int]),
     "csmp_gomp_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, i64, i64, C.c_double, vp, vp, vp, C.c_int]),
@@ -576,6 +578,41 @@ class Context:
     def mp_batch_device(self, B, k, idx, val, nnz):
         """torch CUDA tensors as in omp_batch_device.  Only enqueues work; call sync()."""
         self._batch_device("csmp_mp_batch", B, k, (i64(int(k)),), idx, val, nnz)
+
+    def _somp_call(self, B, code, ldB, nsig, b_loc, k, eps, p):
+        """csmp_somp with the outputs on the host -> (idx, val n x nsig, info)"""
+        kk = max(int(k), 1)
+        idx, order = np.zeros(kk, np.int64), np.zeros(kk, np.int64)
+        val = np.zeros((kk, max(nsig, 1)), np.float64, order="F")
+        resnorm = np.zeros(max(nsig, 1), np.float64)
+        nnz, passes = i64(0), i64(0)
+        self.call("csmp_somp", B, code, i64(ldB), i64(nsig), b_loc, i64(int(k)), C.c_double(eps), int(p), ptr(idx), ptr(val), i64(kk),
+                  C.byref(nnz), ptr(order), ptr(resnorm), C.byref(passes), HOST)
+        n = nnz.value
+        info = {"order": order[:n].copy(), "resnorm": resnorm[:nsig].copy(), "steps": n, "passes": passes.value}
+        return idx[:n].copy(), np.asfortranarray(val[:n, :nsig]), info
+
+    def somp(self, B, k, eps, p=1):
+        """csmp_somp on the host matrix B (M x nsig): simultaneous OMP, ONE support for all columns -> (idx n ascending, val n x nsig
+        whose row i belongs to atom idx[i], info = order (the atoms as they were picked), resnorm float64[nsig], steps, passes)."""
+        B = np.asfortranarray(B)
+        if B.dtype not in (np.float32, np.float64):
+            B = B.astype(np.float64)
+        if B.ndim != 2 or B.shape[0] != self.M:
+            raise CsmpError(EDIM, f"size(B) = {B.shape} but size(A, 1) = {self.M}")
+        return self._somp_call(ptr(B), dtype_code(B.dtype), max(self.M, 1), B.shape[1], HOST, k, eps, p)
+
+    def somp_device(self, B, k, eps, p=1):
+        """as somp, on a torch CUDA matrix whose COLUMNS are the signals: B (M, nsig) float32 / float64 with stride (1, ldB >= M).
+        The results come back as somp's host arrays; the work is done when the call returns."""
+        import torch
+        if not (B.is_cuda and B.dim() == 2 and B.shape[0] == self.M and B.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "B must be a CUDA matrix of size(A, 1) rows, float32 or float64")
+        nsig = B.shape[1]
+        ldB = B.stride(1) if nsig > 1 else max(self.M, 1)
+        if (self.M > 1 and B.stride(0) != 1) or ldB < self.M:
+            raise CsmpError(EDIM, "B must be column-major: unit row stride, a column stride of at least its row count")
+        return self._somp_call(vp(B.data_ptr()), F32 if B.dtype == torch.float32 else F64, ldB, nsig, DEVICE, k, eps, p)
 
     def gomp_batch(self, B, l, k, eps):
         """Host matrix B (M x nsig, column-major) -> (idx k x nsig, val, nnz): gomp for every column, two solves in flight."""

@@ -929,6 +929,43 @@ def mp_batch(A, B, k):
             D.close()
 
 
+def somp(A, B, *args, max_residual=None, sparsity=None, p=1, return_info=False):
+    """somp(A,B,k) | somp(A,B,eps[,k]) | somp(A,B; max_residual=eps(T), sparsity=min(size(A)...), p=1): simultaneous OMP (Tropp, Gilbert
+    and Strauss 2006) for columns of B that share ONE support -- omp's driver with the residual matrix in place of the residual: a step
+    takes the atom that maximises sum_l |<a_j, r_l>|^p (p = 1 or 2), appends it to one factorisation and projects every residual; it ends
+    after k atoms or once ||R||_F < eps (include/csmp.h, csmp_somp).  One column is omp.  Returns a list of SparseVectors that all carry
+    the same nzind (entries that are exactly zero stay in); return_info=True: (xs, info) with order (the atoms as they were picked),
+    resnorm (||r_l|| per column), steps and passes (the passes over the dictionary)."""
+    M, N, eps0 = _meta(A)
+    if len(args) == 0:
+        eps = eps0 if max_residual is None else max_residual
+        k = min(M, N) if sparsity is None else sparsity
+    elif len(args) == 1 and _is_int(args[0]):
+        eps, k = eps0, args[0]
+    elif len(args) == 1:
+        eps, k = args[0], min(M, N)
+    elif len(args) == 2:
+        eps, k = args
+    else:
+        raise TypeError("somp(A, B, [eps,] k)")
+    _check_eps(eps)
+    if not _is_int(k) or not 1 <= k <= min(M, N):
+        raise ValueError(f"k = {k} has to lie in 1 .. min(size(A)) = {min(M, N)}")
+    if not _is_int(p) or p not in (1, 2):
+        raise ValueError(f"p = {p} has to be 1 or 2")
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] != M:
+        raise ValueError(f"size(B) = {B.shape} but size(A, 1) = {M}: B holds one signal per column")
+    D, tmp = _dict(A)
+    try:
+        idx, val, info = D.ctx.somp(B, int(k), float(eps), int(p))
+        xs = [SparseVector(N, idx.copy(), val[:, s].copy()) for s in range(B.shape[1])]
+        return (xs, info) if return_info else xs
+    finally:
+        if tmp:
+            D.close()
+
+
 def gomp_batch(A, B, l, k, eps=None):
     """[gomp(A, B[:, s], l, eps, k) for s in axes(B, 2)] on one GPU (two solves in flight): list of SparseVectors."""
     eps = _meta(A)[2] if eps is None else eps

@@ -23,6 +23,7 @@
 #include "csmp_bpd.hpp"
 #include "csmp_sbl.hpp"
 #include "csmp_fsbl.hpp"
+#include "csmp_somp.hpp"
 
 #include <algorithm>
 #include <iterator>
@@ -50,6 +51,7 @@ using namespace csmp;
 #include "host/omp.hpp"
 #include "host/forward.hpp"
 #include "host/mp_batch.hpp"
+#include "host/somp.hpp"
 #include "host/steps_sharding.hpp"
 #include "host/removal.hpp"
 #include "host/gomp_sp.hpp"

@@ -203,21 +203,34 @@ template <typename TA>
 static hipError_t wide_launch(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t lds, bool nt = kWideNt) {
     return nt ? wide_launch_nt<TA, true>(ctx, p, lds) : wide_launch_nt<TA, false>(ctx, p, lds);
 }
-// the members [first, first + size) step 3 of the slots from slot0 as a pass's entries: up to kGroupMax of them the narrow pass's
-// [0, n); more, the wide pass's halves [0, n) and [kGroupMax, kGroupMax + n1).  Entries past a half's members repeat its last one
-// (the narrow pass never reads them; the wide pass stages their image and masks them).  need_c false: EVERY cvec entry null -- the
-// pass stages and stores no c (sweep_body_multi, sweep_body_multi_w4).
-template <typename TA>
-static void multi_members(csmp_ctx* ctx, MultiSweep<TA>& p, int slot0, int size, bool need_c) {
+// what a pass reads and writes of ONE member: its residual, where its c goes, its arg-max partials, its control block
+struct PassMember {
+    const double* r; double* cvec; double* pval; int* pidx; DevState* st;
+};
+static PassMember slot_member(csmp_ctx* ctx, int q) {
+    const Solver& s = *slot_ptr(ctx, q);
+    return PassMember{s.r, s.cvec, s.pval, s.pidx, s.st};
+}
+// the `size` members member(0), member(1), ... as a pass's entries: up to kGroupMax of them the narrow pass's [0, n); more, the wide
+// pass's halves [0, n) and [kGroupMax, kGroupMax + n1).  Entries past a half's members repeat its last one (the narrow pass never
+// reads them; the wide pass stages their image and masks them).  need_c false: EVERY cvec entry null -- the pass stages and stores
+// no c (sweep_body_multi, sweep_body_multi_w4).
+template <typename TA, typename Member>
+static void multi_members_of(MultiSweep<TA>& p, int size, bool need_c, Member&& member) {
     const bool wide = size > kGroupMax;
     p.n = wide ? (size + 1) / 2 : size;
     p.n1 = wide ? size / 2 : 0;
     for (int e = 0; e < kWideMax; ++e) {
         const int h = e / kGroupMax, i = e % kGroupMax;
         const int m = h == 0 || !wide ? std::min(i, p.n - 1) : p.n + std::min(i, p.n1 - 1);
-        const Solver& s = *slot_ptr(ctx, slot0 + 3 * m);
+        const PassMember s = member(m);
         p.r[e] = s.r; p.cvec[e] = need_c ? s.cvec : nullptr; p.pval[e] = s.pval; p.pidx[e] = s.pidx; p.st[e] = s.st;
     }
+}
+// the schedulers' members: [first, first + size) step 3 of the slots from slot0
+template <typename TA>
+static void multi_members(csmp_ctx* ctx, MultiSweep<TA>& p, int slot0, int size, bool need_c) {
+    multi_members_of<TA>(p, size, need_c, [&](int m) { return slot_member(ctx, slot0 + 3 * m); });
 }
 // Float32: the 512-thread pair body, whose unit is its own (4 loads per column); Float64: the four-wave body on ctx->sweep_U
 template <typename TA>
@@ -237,15 +250,16 @@ static hipError_t multi_launch(csmp_ctx* ctx, const MultiSweep<TA>& p, size_t ld
 // step of csmp_mp_batch's groups (mp_group_step, host/mp_batch.hpp).  need_c: the pass writes every member's c = A'r to its slot's
 // cvec.  k_mp_group reads c there; the grouped OMP scheduler's append stage (k_append_group: qr1_body) takes its atom from the
 // pass's partials and k_finish_group reads R, z and the selection, so its passes store none (2.4 GB a call of 18 signals, k = 256, at
-// N = 65536) unless csmp_tune pass_c asks for them.
-template <typename TA>
-static int shared_pass_launch(csmp_ctx* ctx, int slot0, int size, double eps, int check_eps, int skipmask, int nblk, int nblk_wide,
-                              size_t lds_sweep, bool need_c) {
+// N = 65536) unless csmp_tune pass_c asks for them.  shared_pass_launch_of: the same launch for members that live elsewhere
+// (csmp_somp's columns, host/somp.hpp).
+template <typename TA, typename Member>
+static int shared_pass_launch_of(csmp_ctx* ctx, int size, double eps, int check_eps, int skipmask, int nblk, int nblk_wide, size_t lds_sweep,
+                                 bool need_c, Member&& member) {
     MultiSweep<TA> p;
     p.A = (const TA*)ctx->dA; p.ld = ctx->ld; p.Mv = ctx->Mv; p.N = ctx->N;
     const bool wide = size > kGroupMax;
     p.eps = eps; p.check_eps = check_eps; p.skipmask = skipmask; p.nblk = wide ? nblk_wide : nblk; p.KP = ctx->sweep_KP;
-    multi_members<TA>(ctx, p, slot0, size, need_c);
+    multi_members_of<TA>(p, size, need_c, member);
     // ONE sampled launch per shared pass: it reads A once, whatever the group size
     const bool timed = prof_pick(ctx);
     if (timed) CHECK(prof_mark(ctx));
@@ -253,6 +267,12 @@ static int shared_pass_launch(csmp_ctx* ctx, int slot0, int size, double eps, in
     HIPCHECK(wide ? wide_launch<TA>(ctx, p, lds) : multi_launch<TA>(ctx, p, lds));
     if (timed) CHECK(prof_mark(ctx));
     return CSMP_OK;
+}
+template <typename TA>
+static int shared_pass_launch(csmp_ctx* ctx, int slot0, int size, double eps, int check_eps, int skipmask, int nblk, int nblk_wide,
+                              size_t lds_sweep, bool need_c) {
+    return shared_pass_launch_of<TA>(ctx, size, eps, check_eps, skipmask, nblk, nblk_wide, lds_sweep, need_c,
+                                     [&](int m) { return slot_member(ctx, slot0 + 3 * m); });
 }
 template <typename TA>
 static int group_pipe_launch(Pipe& gp, int64_t n) {

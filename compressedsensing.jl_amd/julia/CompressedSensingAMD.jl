@@ -863,6 +863,32 @@ function mp_batch(A::MatOrDict{T}, B::StridedMatrix, k::Int) where {T}
     [to_sparse(size(A, 2), idx[:, s], val[:, s], nnz[s]) for s in 1:nsig]
 end
 
+# somp(A, B, ε, k; p): simultaneous OMP for columns of B that share ONE support (Tropp, Gilbert and Strauss 2006) -- omp's driver with the
+# residual matrix in place of the residual: the atom that maximises sum_l |<a_j, r_l>|^p, one append, every residual projected
+# (csmp_somp).  Returns SparseVectors that all carry the same nzind; return_info: (xs, (order, resnorm, steps, passes)).
+function somp(A::MatOrDict{T}, B::AbstractMatrix, ε::Real, k::Int = min(size(A)...); p::Int = 1, return_info::Bool = false) where {T}
+    ε ≥ 0 || throw(ArgumentError("ε = $ε has to be non-negative"))
+    p in (1, 2) || throw(ArgumentError("p = $p has to be 1 or 2"))
+    D = dict(A)
+    BB = B isa StridedMatrix && eltype(B) <: Union{Float32,Float64} && stride(B, 1) == 1 ? B : convert(Matrix{Float64}, B)
+    size(BB, 1) == size(D, 1) || throw(DimensionMismatch("size(B, 1) = $(size(BB, 1)) but size(A, 1) = $(size(D, 1))"))
+    1 <= k <= min(size(D, 1), size(D, 2)) || throw(ArgumentError("k = $k has to lie in 1:min(size(A)...)"))
+    nsig = size(BB, 2)
+    idx, order, val = zeros(Int64, k), zeros(Int64, k), zeros(Float64, k, max(nsig, 1))
+    resnorm, nnz, passes = zeros(Float64, max(nsig, 1)), Ref{Int64}(0), Ref{Int64}(0)
+    GC.@preserve BB idx val order resnorm check(D, ccall((:csmp_somp, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Int64, Cdouble, Cint, Ptr{Int64}, Ptr{Cdouble}, Int64, Ref{Int64}, Ptr{Int64},
+         Ptr{Cdouble}, Ref{Int64}, Cint),
+        D.ctx, BB, dtype_code(eltype(BB)), max(stride(BB, 2), size(BB, 1)), nsig, CSMP_HOST, k, ε, p, idx, val, k, nnz, order, resnorm, passes,
+        CSMP_HOST))
+    n = Int(nnz[])
+    xs = [SparseVector(size(D, 2), idx[1:n] .+ 1, val[1:n, s]) for s in 1:nsig]
+    return return_info ? (xs, (order = order[1:n] .+ 1, resnorm = resnorm[1:nsig], steps = n, passes = Int(passes[]))) : xs
+end
+somp(A::MatOrDict{T}, B::AbstractMatrix, k::Int; kw...) where {T} = somp(A, B, eps(T), k; kw...)
+somp(A::MatOrDict{T}, B::AbstractMatrix; max_residual = eps(T), sparsity = min(size(A)...), kw...) where {T} =
+    somp(A, B, max_residual, sparsity; kw...)
+
 # [gomp(A, B[:, s], l, eps, k) for s in axes(B, 2)]: two solves in flight on two streams (csmp_gomp_batch)
 function gomp_batch(A::MatOrDict{T}, B::StridedMatrix, l::Int, ε::Real, k::Int) where {T}
     D = dict(A)

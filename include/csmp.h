@@ -224,6 +224,30 @@ int csmp_fr_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_
 int csmp_mp_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k, int64_t *idx,
                   double *val, int64_t *nnz, int out_loc);
 
+/* somp(A, B, eps, k; p): simultaneous OMP (S-OMP: Tropp, Gilbert and Strauss 2006) for columns of B that share ONE support -- trials
+ * of one experiment, frames of one scene, channels of one array.  omp's driver (src/matchingpursuit.jl:62-82) with the residual
+ * matrix R in place of r: a step scores every atom by s_j = sum_l |<a_j, r_l>|^p, p = 1 or 2 (the correlations are the sweeps' bits,
+ * added in column order), takes the arg-max (the lowest index among equals) under omp's guards -- the support smaller than
+ * size(A,1) and than k, the atom not in it yet: a pick inside the support ends the solve --, appends that atom to ONE CGS2
+ * factorisation (the append chain with its second Gram-Schmidt pass) and projects every residual off the new direction; from the
+ * second step on the solve ends once ||R||_F < eps.  At the end R_fac X_S = Z is solved for all columns.  One column is omp.
+ * B: ldB x nsig, column-major, host or device memory (b_loc).  Outputs in host or device memory (out_loc): idx (k), the support in
+ * ascending order; val (ldval x nsig, ldval >= k), row i the coefficients of atom idx[i] in every column, entries that are exactly
+ * zero included; order (k, may be NULL), the atoms in the order they were picked; resnorm (nsig, may be NULL), ||r_l|| of every
+ * column.  Unused tails of idx and order are -1, of val 0.  nnz and passes (may be NULL) are HOST scalars: the size of the support
+ * (the steps taken), and the passes over the dictionary that ran.  The call returns with the work done.
+ * The residuals go through the shared pass of csmp_mp_batch in chunks of up to group_wide columns (8 on Float32 dictionaries, 4 on
+ * Float64; csmp_tune group_max / group_wide apply): ceil(nsig / group_wide) passes a step, ONE append a step whatever nsig is.  Where
+ * the resident dictionary has no shared pass (phased sweeps, the dynamic-sweep switch, a host-streamed dictionary) a step takes
+ * one sweep per column: the same results.  CSMP_OPT_SCREENED_SWEEP is ignored: the sweeps are exact.  nsig is bounded by device
+ * memory only, 8 (size(A,1) + size(A,2) + k) bytes a column.  The same bits on every run, for every chunking.
+ * CSMP_EINVAL: NULL arguments, k < 1, nsig < 0, eps negative or NaN, p neither 1 nor 2, ldB < size(A,1), ldval < k, a bad b_dtype,
+ * b_loc or out_loc.  CSMP_ERANGE: k > min(size(A)).  CSMP_ESTATE: no dictionary.  CSMP_ENOMEM: the columns' buffers could not be
+ * allocated; everything is freed, the context stays usable.  nsig == 0: CSMP_OK, nothing is written. */
+int csmp_somp(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc, int64_t k, double eps, int p,
+              int64_t *idx, double *val, int64_t ldval, int64_t *nnz, int64_t *order, double *resnorm, int64_t *passes,
+              int out_loc);
+
 /* gomp(A, B[:,s], l, eps, k) for s = 0..nsig-1 (src/matchingpursuit.jl:116-139 in the caller's loop), 1 <= l <= k: the conventions
  * of csmp_omp_batch (idx / val: k x nsig).  TWO solves are in flight, one on the context's stream and one on an internal clone's,
  * out of phase: a signal's short stages (top-l selection, the l-column panel append) run under the other signal's dictionary
