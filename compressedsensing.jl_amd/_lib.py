@@ -86,6 +86,8 @@ SIGNATURES = {
     "csmp_ista": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, i64, i64, C.c_double, C.c_int, vp, C.c_int, C.POINTER(C.c_double)]),
     "csmp_ista_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, vp, i64, i64, vp, i64, i64, C.c_double, C.c_int, vp, i64, C.c_int,
                                   C.POINTER(C.c_double)]),
+    "csmp_ista_joint": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, vp, i64, vp, i64, i64, C.c_double, C.c_int, vp, i64, C.c_int,
+                                  C.POINTER(i64), C.POINTER(C.c_double)]),
     "csmp_ard_weights": (C.c_int, [vp, vp, vp, C.c_double, i64, vp, C.c_int]),
     "csmp_ista_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, i64, i64, C.c_double, i64, C.c_double, C.c_int, vp, C.c_int, vp,
                                        C.POINTER(i64), C.POINTER(C.c_double)]),
@@ -865,6 +867,64 @@ class Context:
                 raise CsmpError(EDIM, f"{name} must be column-major: unit row stride, a column stride of at least its row count")
             lds.append(ld)
         return self._ista_batch_call(vp(B.data_ptr()), F32 if B.dtype == torch.float32 else F64, ldB, nsig, DEVICE, w,
+                                     None if X0 is None else vp(X0.data_ptr()), lds[1], vp(X.data_ptr()), lds[0], DEVICE, maxiter, stepsize, accel)
+
+    def _ista_joint_call(self, B, code, ldB, nsig, b_loc, w, X0, ldX0, X, ldX, x_loc, maxiter, stepsize, accel):
+        w = np.atleast_1d(np.asarray(w, dtype=np.float64))
+        if w.ndim != 1:
+            raise CsmpError(EDIM, "the weights must be a scalar or a vector (one weight per row of X)")
+        w = np.ascontiguousarray(w)
+        rn = np.zeros(max(nsig, 1), np.float64)
+        rows = i64(0)
+        self.call("csmp_ista_joint", B, code, i64(ldB), i64(nsig), b_loc, ptr(w), i64(len(w)), X0, i64(ldX0), i64(int(maxiter)),
+                  C.c_double(stepsize), int(bool(accel)), X, i64(ldX), x_loc, C.byref(rows), rn.ctypes.data_as(C.POINTER(C.c_double)))
+        return {"rows": int(rows.value), "resnorm": rn[:nsig]}
+
+    def ista_joint(self, B, w, X0=None, maxiter=1024, stepsize=1e-2, accel=False):
+        """csmp_ista_joint on the host matrix B (M x nsig): ista (accel: fista) on ||B - A X||_F^2 + sum_j w_j ||X[j, :]||_2, ONE row
+        support for all columns -- (X, Float64 N x nsig in Fortran order; info = rows (the non-zero rows of X), resnorm float64[nsig]).
+        w: a scalar or an N-vector (one weight per row).  X0: None, or the dense N x nsig warm start.  One column is ista."""
+        B = np.asfortranarray(B)
+        if B.dtype not in (np.float32, np.float64):
+            B = B.astype(np.float64)
+        if B.ndim != 2 or B.shape[0] != self.M:
+            raise CsmpError(EDIM, f"size(B) = {B.shape} but size(A, 1) = {self.M}")
+        nsig = B.shape[1]
+        ld = max(self.N, 1)
+        X = np.zeros((ld, nsig), np.float64, order="F")
+        if X0 is not None:
+            X0 = np.asarray(X0, dtype=np.float64)
+            if X0.shape != (self.N, nsig):
+                raise CsmpError(EDIM, f"size(X0) = {X0.shape} but the warm start is size(A, 2) x nsig = {(self.N, nsig)}")
+            X[:self.N] = X0  # (continued in place: X0 == X)
+        info = self._ista_joint_call(ptr(B), dtype_code(B.dtype), max(self.M, 1), nsig, HOST, w, None if X0 is None else ptr(X), ld, ptr(X), ld,
+                                     HOST, maxiter, stepsize, accel)
+        return X[:self.N], info
+
+    def ista_joint_device(self, B, w, X, X0=None, maxiter=1024, stepsize=1e-2, accel=False):
+        """torch CUDA tensors whose COLUMNS are the signals and the results, with ista_batch_device's stride rules: B (M, nsig) float32 /
+        float64 with stride (1, ldB >= M), X and (optionally) X0 (N, nsig) float64 with stride (1, ld >= N); X0 may be X itself (a run
+        continued in place) and must not overlap it otherwise.  w: as ista_joint, on the host.  Returns info; the work is done when the
+        call returns."""
+        import torch
+        if not (B.is_cuda and B.dim() == 2 and B.shape[0] == self.M and B.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "B must be a CUDA matrix of size(A, 1) rows, float32 or float64")
+        nsig = B.shape[1]
+        ldB = B.stride(1) if nsig > 1 else max(self.M, 1)
+        if (self.M > 1 and B.stride(0) != 1) or ldB < self.M:
+            raise CsmpError(EDIM, "B must be column-major: unit row stride, a column stride of at least its row count")
+        lds = []
+        for name, T in (("X", X), ("X0", X0)):
+            if T is None:
+                lds.append(max(self.N, 1))
+                continue
+            if not (T.is_cuda and T.dim() == 2 and T.shape == (self.N, nsig) and T.dtype == torch.float64):
+                raise CsmpError(EDIM, f"{name} must be a CUDA float64 matrix of size(A, 2) rows and B's columns")
+            ld = T.stride(1) if nsig > 1 else max(self.N, 1)
+            if (self.N > 1 and T.stride(0) != 1) or ld < self.N:
+                raise CsmpError(EDIM, f"{name} must be column-major: unit row stride, a column stride of at least its row count")
+            lds.append(ld)
+        return self._ista_joint_call(vp(B.data_ptr()), F32 if B.dtype == torch.float32 else F64, ldB, nsig, DEVICE, w,
                                      None if X0 is None else vp(X0.data_ptr()), lds[1], vp(X.data_ptr()), lds[0], DEVICE, maxiter, stepsize, accel)
 
     # ---- reweighted l1

@@ -241,6 +241,58 @@ def fista_batch(A, B, lam_or_w, X0=None, *, maxiter=1024, stepsize=1e-2):
     return _ista_batch(A, B, lam_or_w, X0, maxiter, stepsize, True)
 
 
+def _ista_joint(A, B, lam_or_w, X0, maxiter, stepsize, accel, return_info):
+    M, N, _ = _meta(A)
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] != M:
+        raise ValueError(f"size(B) = {B.shape} but size(A, 1) = {M}: B holds one signal per column")
+    nsig = B.shape[1]
+    w = np.atleast_1d(np.asarray(lam_or_w, dtype=np.float64))
+    if w.ndim != 1 or len(w) not in (1, N):
+        raise ValueError(f"length(w) = {w.shape} but size(A, 2) = {N}: one weight, or one per row of X")
+    if not np.all((w >= 0) & np.isfinite(w)):
+        raise ValueError("the weights have to be non-negative and finite")
+    if not maxiter >= 0:
+        raise ValueError(f"maxiter = {maxiter} has to be non-negative")
+    if not (stepsize > 0 and np.isfinite(stepsize)):
+        raise ValueError(f"stepsize = {stepsize} has to be positive and finite")
+    if X0 is not None:
+        if isinstance(X0, (list, tuple)):
+            if len(X0) != nsig or any(getattr(x, "n", None) != N for x in X0):
+                raise ValueError(f"X0 has to hold {nsig} SparseVectors of length {N}")
+            dense = np.zeros((N, nsig), np.float64, order="F")
+            for s, x in enumerate(X0):
+                dense[x.nzind, s] = x.nzval
+            X0 = dense
+        else:
+            X0 = np.asarray(X0, dtype=np.float64)
+            if X0.shape != (N, nsig):
+                raise ValueError(f"size(X0) = {X0.shape} but the warm start is size(A, 2) x nsig = {(N, nsig)}")
+    D, tmp = _dict(A)
+    try:
+        X, info = D.ctx.ista_joint(B, w, X0, maxiter=int(maxiter), stepsize=float(stepsize), accel=accel)
+        nz = np.flatnonzero(np.any(X != 0, axis=1))  # the non-zero rows: ONE support (entries that are exactly zero stay in)
+        xs = [SparseVector(N, nz.copy(), X[nz, s].copy()) for s in range(nsig)]
+        return (xs, info) if return_info else xs
+    finally:
+        if tmp:
+            D.close()
+
+
+def ista_joint(A, B, lam_or_w, X0=None, *, maxiter=1024, stepsize=1e-2, return_info=False):
+    """ista for columns of B that share ONE support: exactly maxiter steps of the proximal-gradient iteration on the row-sparse (l2,1)
+    objective ‖B − A X‖_F² + Σ_j w_j ‖X[j, :]‖₂ -- U = X + 2α Aᵀ(B − A X), X⁺[j, :] = max(1 − w_j α / ‖U[j, :]‖₂, 0) U[j, :] (include/csmp.h,
+    csmp_ista_joint).  The convex counterpart of somp; one column is ista.  lam_or_w: a scalar or an N-vector (one weight per ROW of X).
+    X0: the warm start, a list of SparseVectors or a dense N x nsig matrix (not changed).  Returns a list of SparseVectors that all carry
+    the same nzind (the non-zero rows); return_info=True: (xs, info) with rows (their number) and resnorm (‖b_l − A x_l‖ per column)."""
+    return _ista_joint(A, B, lam_or_w, X0, maxiter, stepsize, False, return_info)
+
+
+def fista_joint(A, B, lam_or_w, X0=None, *, maxiter=1024, stepsize=1e-2, return_info=False):
+    """ista_joint with fista's acceleration: Y⁺ = X⁺ + ((t − 1)/t⁺)(X⁺ − X), t₁ = 1, the step taken from Y."""
+    return _ista_joint(A, B, lam_or_w, X0, maxiter, stepsize, True, return_info)
+
+
 # ------------------------------------------------------------------------------------ reweighted l1
 def candes_weights(x, eps=1e-2):
     """candes_weights!(w, x, ε): w_j = 1 / (|x_j| + ε) (src/basispursuit.jl:33-39), Float64[N]; x a vector or a SparseVector.  NaN or Inf

@@ -24,6 +24,7 @@
 #include "csmp_sbl.hpp"
 #include "csmp_fsbl.hpp"
 #include "csmp_somp.hpp"
+#include "csmp_ista_joint.hpp"
 
 #include <algorithm>
 #include <iterator>
@@ -69,6 +70,7 @@ using namespace csmp;
 #include "host/bpd.hpp"
 #include "host/bpd_batch.hpp"
 #include "host/ista_batch.hpp"
+#include "host/ista_joint.hpp"
 #include "host/sbl.hpp"
 #include "host/fsbl.hpp"
 #include "host/fsbl_batch.hpp"

@@ -223,6 +223,38 @@ ista_batch(A::MatOrDict, B::AbstractMatrix, w::Union{Real,AbstractVecOrMat}, X0:
 fista_batch(A::MatOrDict, B::AbstractMatrix, w::Union{Real,AbstractVecOrMat}, X0::Union{Nothing,AbstractMatrix} = nothing; maxiter::Int = 1024,
             stepsize::Real = 1e-2) = ista_batch_call(A, B, ista_batch_weights(A, B, w)..., X0, maxiter, stepsize, true)
 
+# ista / fista for columns of B that share ONE support: the row-sparse (l2,1) objective ‖B - A X‖_F² + Σ_j w_j ‖X[j, :]‖₂, the convex
+# counterpart of somp (csmp_ista_joint).  The weights: a λ, or one weight per ROW of X.  X0: the dense warm start, N x nsig.  Returns
+# SparseVectors that all carry the same nzind (the non-zero rows); return_info: (xs, (rows, resnorm)).
+function ista_joint_call(A::MatOrDict, B::AbstractMatrix, w::Vector{Float64}, X0::Union{Nothing,AbstractMatrix}, maxiter::Int, stepsize::Real,
+                         accel::Bool, return_info::Bool)
+    D = dict(A)
+    BB = B isa StridedMatrix && eltype(B) <: Union{Float32,Float64} && stride(B, 1) == 1 ? B : convert(Matrix{Float64}, B)
+    size(BB, 1) == size(D, 1) || throw(DimensionMismatch("size(B, 1) = $(size(BB, 1)) but size(A, 1) = $(size(D, 1))"))
+    nsig, N = size(BB, 2), size(D, 2)
+    length(w) in (1, N) || throw(DimensionMismatch("length(w) = $(length(w)) but size(A, 2) = $N"))
+    X = zeros(Float64, N, nsig)
+    if X0 !== nothing
+        size(X0) == (N, nsig) || throw(DimensionMismatch("size(X0) = $(size(X0)) but the warm start is $N x $nsig"))
+        copyto!(X, X0)  # (continued in place: X0 == X)
+    end
+    rn, rows = zeros(Float64, max(nsig, 1)), Ref{Int64}(0)
+    GC.@preserve BB w X rn check(D, ccall((:csmp_ista_joint, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Int64, Cdouble, Cint, Ptr{Cdouble}, Int64,
+         Cint, Ref{Int64}, Ptr{Cdouble}),
+        D.ctx, BB, dtype_code(eltype(BB)), max(stride(BB, 2), size(BB, 1)), nsig, CSMP_HOST, w, length(w), X0 === nothing ? C_NULL : pointer(X),
+        max(N, 1), maxiter, stepsize, Cint(accel), X, max(N, 1), CSMP_HOST, rows, rn))
+    nz = findall(j -> any(!iszero, view(X, j, :)), 1:N)
+    xs = [SparseVector(N, nz, X[nz, s]) for s in 1:nsig]
+    return return_info ? (xs, (rows = Int(rows[]), resnorm = rn[1:nsig])) : xs
+end
+ista_joint(A::MatOrDict, B::AbstractMatrix, w::Union{Real,AbstractVector}, X0::Union{Nothing,AbstractMatrix} = nothing; maxiter::Int = 1024,
+           stepsize::Real = 1e-2, return_info::Bool = false) =
+    ista_joint_call(A, B, w isa Real ? Float64[w] : convert(Vector{Float64}, w), X0, maxiter, stepsize, false, return_info)
+fista_joint(A::MatOrDict, B::AbstractMatrix, w::Union{Real,AbstractVector}, X0::Union{Nothing,AbstractMatrix} = nothing; maxiter::Int = 1024,
+            stepsize::Real = 1e-2, return_info::Bool = false) =
+    ista_joint_call(A, B, w isa Real ? Float64[w] : convert(Vector{Float64}, w), X0, maxiter, stepsize, true, return_info)
+
 # ---------------------------------------------------------------------------------- reweighted l1
 # src/basispursuit.jl:18-74: candes_weights!, ard_weights! and basispursuit_reweighting with ista / fista as the solver of
 # ‖b - A x‖² + λ Σ w_j |x_j| (the loops around bp and bpd themselves: bp_candes / bp_ard and bpd_candes / bpd_ard below).

@@ -469,6 +469,38 @@ int csmp_ista_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int6
                     int64_t maxiter, double stepsize, int accel, double *X, int64_t ldX, int x_loc,
                     double *resnorm);
 
+/* ista_joint: ISTA / FISTA on the row-sparse (l2,1, "group lasso over rows", MMV) objective
+ *     ||B - A X||_F^2 + sum_j w_j ||X[j, :]||_2
+ * for columns of B that share ONE support -- the convex counterpart of csmp_somp.  One iteration, alpha = stepsize, t_j = w_j alpha:
+ *     R = B - A Y;  C = A'R;  U = Y + 2 alpha C;  n_j = sqrt(sum_l U[j,l]^2), added in column order l = 0, 1, ...;
+ *     X+[j,:] = 0 exactly where !(n_j > t_j), else (1 - t_j / n_j) U[j,:].
+ * accel = 0 (ISTA): Y+ = X+.  accel = 1 (FISTA): Y+ = X+ + beta (X+ - X) with csmp_ista's recurrence, t_1 = 1, Y_1 = X_0.  Exactly
+ * maxiter iterations, no stopping rule, nothing read back in between; maxiter = 0 returns the warm start.
+ * B: size(A,1) x nsig, column-major, leading dimension ldB >= size(A,1), CSMP_F32 or CSMP_F64, on the host or the device (b_loc).
+ * w, nw: a host array; nw = 1 (one lambda) or size(A,2) (one weight per ROW of X); non-negative and finite.
+ * X0, ldX0: NULL starts from zero.  Otherwise a dense size(A,2) x nsig matrix of doubles where X lives (x_loc), ldX0 >= size(A,2).
+ * X0 == X with ldX0 == ldX continues a run in place; any other overlap of X0 and X is the caller's error and is not detected.
+ * X: size(A,2) x nsig doubles, leading dimension ldX >= size(A,2), on the host or the device (x_loc); rows beyond size(A,2) are not
+ * touched.  nrows (may be NULL): the number of non-zero rows of X.  resnorm (may be NULL): a host array, ||b_l - A x_l||_2 per column
+ * (||b_l|| for maxiter = 0 without a warm start).  nsig = 0: CSMP_OK, nothing is touched.
+ * One column is csmp_ista: nsig = 1 takes csmp_ista's own launches and returns its bits.  More columns: the passes for C are
+ * csmp_somp's (chunks of up to group_wide columns on the shared pass, csmp_tune group_max / group_wide apply; one sweep per column for
+ * a dictionary without a shared pass; CSMP_OPT_SCREENED_SWEEP is ignored), and the residual reads every live column of A ONCE for a
+ * chunk of up to eight columns of B, because there is one list for all of them.
+ * Arithmetic: Float64 on the exactly promoted dictionary values, no floating-point atomics, every sum in a fixed order: the same call
+ * returns the same bits every time, whatever the chunks are, and equal columns of B give equal columns of X.
+ * Memory: the call's own, released when it returns -- 8 (2 size(A,1) + 4 size(A,2)) bytes a column (size(A,1) rounded up to 256 rows)
+ * and one chunk's partial sums of the residual (128 MiB at 4096 x 65536); nsig is bounded by memory only.
+ * CSMP_EINVAL: nsig < 0, null pointers, a dtype / location that is neither, accel other than 0 or 1, maxiter < 0, a stepsize that is
+ * not positive and finite, a negative or non-finite weight.  CSMP_EDIM: ldB < size(A,1), ldX < size(A,2), ldX0 < size(A,2), nw other
+ * than 1 or size(A,2).  CSMP_ERANGE: nsig > 2^22.  CSMP_ESTATE: no dictionary, or a host-streamed one (as csmp_ista).  CSMP_ENOMEM: a
+ * buffer could not be allocated; no partial buffers are left behind and the context stays usable.  Everything is validated before
+ * any device work.  A refused call writes nothing. */
+int csmp_ista_joint(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc,
+                    const double *w, int64_t nw, const double *X0, int64_t ldX0,
+                    int64_t maxiter, double stepsize, int accel,
+                    double *X, int64_t ldX, int x_loc, int64_t *nrows, double *resnorm);
+
 /* ------------------------------------------------------------------ reweighted l1
  * candes_weights! / ard_weights! / basispursuit_reweighting: src/basispursuit.jl:18-74 (bp_candes, bp_ard; bpd_candes, bpd_ard :102-124),
  * with ista / fista as the inner solver (the reference's own inner solvers, bp and bpd, are csmp_bp and csmp_bpd below: neither needs
