@@ -95,6 +95,8 @@ SIGNATURES = {
                           C.POINTER(C.c_int)]),
     "csmp_bp_batch": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, vp, i64, C.c_double, i64, C.c_double, i64, vp, i64, C.c_int, C.POINTER(i64),
                                 C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "csmp_bp_joint": (C.c_int, [vp, vp, C.c_int, i64, i64, C.c_int, vp, i64, C.c_double, i64, C.c_double, i64, vp, i64, C.c_int, C.POINTER(i64),
+                                C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "csmp_bp_reweighted": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_double, i64, i64, C.c_double, C.c_double, i64, C.c_double, i64, vp, C.c_int, vp,
                                      C.POINTER(i64), C.POINTER(C.c_double)]),
     "csmp_bpd": (C.c_int, [vp, vp, C.c_int, C.c_double, vp, i64, C.c_double, i64, C.c_double, i64, vp, C.c_int, C.POINTER(i64), C.POINTER(C.c_double),
@@ -1045,6 +1047,47 @@ class Context:
         if (self.M > 1 and B.stride(0) != 1) or (self.N > 1 and X.stride(0) != 1) or ldB < self.M or ldX < self.N:
             raise CsmpError(EDIM, "B and X must be column-major: unit row stride, column strides of at least their row counts")
         return self._bp_batch_call(vp(B.data_ptr()), F32 if B.dtype == torch.float32 else F64, ldB, nsig, DEVICE, w, vp(X.data_ptr()), ldX, DEVICE,
+                                   rho, maxiter, tol, check_every)
+
+    def _bp_joint_call(self, B, code, ldB, nsig, b_loc, w, X, ldX, x_loc, rho, maxiter, tol, check_every):
+        w, _, _ = self._ista_args(w, None, None)
+        rn = np.zeros(max(nsig, 1), np.float64)
+        it, rows, flags = i64(0), i64(0), C.c_int(0)
+        self.call("csmp_bp_joint", B, code, i64(ldB), i64(nsig), b_loc, ptr(w), i64(len(w)), C.c_double(rho), i64(int(maxiter)), C.c_double(tol),
+                  i64(int(check_every)), X, i64(ldX), x_loc, C.byref(it), C.byref(rows), rn.ctypes.data_as(C.POINTER(C.c_double)), C.byref(flags))
+        return {"iterations": int(it.value), "converged": bool(flags.value & BP_CONVERGED), "factored": bool(flags.value & BP_FACTORED),
+                "rows": int(rows.value), "resnorm": rn[:nsig]}
+
+    def bp_joint(self, B, w=1.0, rho=1.0, maxiter=16384, tol=1e-8, check_every=32):
+        """csmp_bp_joint on the host matrix B (M x nsig): min sum_j w_j ||X[j, :]||_2 subject to A X = B, ONE row support for all columns
+        and ONE stopping rule -- (X, Float64 N x nsig in Fortran order; info = iterations, converged, factored, rows (the non-zero rows of
+        X), resnorm float64[nsig]).  w: one weight or N of them (one per row).  One column is bp."""
+        B = np.asfortranarray(B)
+        if B.dtype not in (np.float32, np.float64):
+            B = B.astype(np.float64)
+        if B.ndim != 2 or B.shape[0] != self.M:
+            raise CsmpError(EDIM, f"size(B) = {B.shape} but size(A, 1) = {self.M}")
+        nsig = B.shape[1]
+        X = np.zeros((max(self.N, 1), nsig), np.float64, order="F")
+        info = self._bp_joint_call(ptr(B), dtype_code(B.dtype), max(self.M, 1), nsig, HOST, w, ptr(X), max(self.N, 1), HOST, rho, maxiter, tol,
+                                   check_every)
+        return X[:self.N], info
+
+    def bp_joint_device(self, B, w, X, rho=1.0, maxiter=16384, tol=1e-8, check_every=32):
+        """torch CUDA tensors whose COLUMNS are the signals and the results, with bp_batch_device's stride rules: B (M, nsig) float32 /
+        float64 with stride (1, ldB >= M), X (N, nsig) float64 with stride (1, ldX >= N).  Returns info; the work is done when the call
+        returns."""
+        import torch
+        if not (B.is_cuda and B.dim() == 2 and B.shape[0] == self.M and B.dtype in (torch.float32, torch.float64)):
+            raise CsmpError(EDIM, "B must be a CUDA matrix of size(A, 1) rows, float32 or float64")
+        nsig = B.shape[1]
+        if not (X.is_cuda and X.dim() == 2 and X.shape == (self.N, nsig) and X.dtype == torch.float64):
+            raise CsmpError(EDIM, "X must be a CUDA float64 matrix of size(A, 2) rows and B's columns")
+        ldB = B.stride(1) if nsig > 1 else max(self.M, 1)
+        ldX = X.stride(1) if nsig > 1 else max(self.N, 1)
+        if (self.M > 1 and B.stride(0) != 1) or (self.N > 1 and X.stride(0) != 1) or ldB < self.M or ldX < self.N:
+            raise CsmpError(EDIM, "B and X must be column-major: unit row stride, column strides of at least their row counts")
+        return self._bp_joint_call(vp(B.data_ptr()), F32 if B.dtype == torch.float32 else F64, ldB, nsig, DEVICE, w, vp(X.data_ptr()), ldX, DEVICE,
                                    rho, maxiter, tol, check_every)
 
     def bp_reweighted(self, b, scheme, eps=1e-2, ard_iter=8, outer_maxiter=8, min_decrease=1e-8, rho=1.0, maxiter=16384, tol=1e-8, check_every=32,

@@ -449,6 +449,39 @@ def bp_batch(A, B, w=None, *, rho=1.0, maxiter=16384, tol=1e-8, check_every=32, 
             D.close()
 
 
+def bp_joint(A, B, w=None, *, rho=1.0, maxiter=16384, tol=1e-8, check_every=32, return_info=False):
+    """bp for columns of B that share ONE support: min Σ_j w_j ‖X[j, :]‖₂ subject to A X = B, the row-sparse (l2,1, "MMV") programme --
+    bp's ADMM with matrices in place of vectors and the shrinkage on whole rows, Z⁺[j, :] = max(1 − w_j / (ρ ‖T[j, :]‖₂), 0) T[j, :]
+    (include/csmp.h, csmp_bp_joint).  No λ and no step size; the equality-constrained companion of ista_joint and the convex
+    counterpart of somp; one column is bp.  ONE stopping rule for all columns: every check_every iterations ‖U⁺ − U‖_F and ρ‖Z⁺ − Z‖_F
+    are read, and the iteration stops once both are below tol.  w: None (ones), a scalar or an N-vector (one weight per ROW of X).
+    Returns a list of SparseVectors that all carry the same nzind (the non-zero rows); return_info=True: (xs, info) with
+    info = {iterations, converged, factored, rows, resnorm (‖b_l − A x_l‖ per column)}.  Reaching maxiter is no error."""
+    M, N = _bp_knobs(A, rho, maxiter, tol, check_every)
+    w = np.ones(1) if w is None else np.atleast_1d(np.asarray(w, dtype=np.float64))
+    if w.ndim != 1 or len(w) not in (1, N):
+        raise ValueError(f"length(w) = {w.shape} but size(A, 2) = {N}: one weight, or one per row of X")
+    if not np.all((w >= 0) & np.isfinite(w)):
+        raise ValueError("the weights have to be non-negative and finite")
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] != M:
+        raise ValueError(f"size(B) = {B.shape} but size(A, 1) = {M}: B holds one signal per column")
+    D, tmp = _dict(A)
+    try:
+        try:
+            X, info = D.ctx.bp_joint(B, w, float(rho), int(maxiter), float(tol), int(check_every))
+        except CsmpError as e:
+            if e.code == _lib.EINVAL and "positive definite" in str(e):
+                raise ValueError(str(e)) from None
+            raise
+        nz = np.flatnonzero(np.any(X != 0, axis=1))  # the non-zero rows: ONE support (entries that are exactly zero stay in)
+        xs = [SparseVector(N, nz.copy(), X[nz, s].copy()) for s in range(X.shape[1])]
+        return (xs, info) if return_info else xs
+    finally:
+        if tmp:
+            D.close()
+
+
 def _bp_reweighted(A, b, scheme, eps, maxiter, min_decrease, rho, inner_maxiter, tol, check_every, return_weights, ard_iter=8):
     M, N = _bp_knobs(A, rho, inner_maxiter, tol, check_every)
     if not (eps > 0 and np.isfinite(eps)):

@@ -25,6 +25,7 @@
 #include "csmp_fsbl.hpp"
 #include "csmp_somp.hpp"
 #include "csmp_ista_joint.hpp"
+#include "csmp_bp_joint.hpp"
 
 #include <algorithm>
 #include <iterator>
@@ -71,6 +72,7 @@ using namespace csmp;
 #include "host/bpd_batch.hpp"
 #include "host/ista_batch.hpp"
 #include "host/ista_joint.hpp"
+#include "host/bp_joint.hpp"
 #include "host/sbl.hpp"
 #include "host/fsbl.hpp"
 #include "host/fsbl_batch.hpp"

@@ -341,6 +341,33 @@ bp_batch(A::MatOrDict, B::AbstractMatrix; rho::Real = 1.0, maxiter::Int = 16384,
     bp_batch_call(A, B, Float64[1.0], rho, maxiter, tol, check_every, return_info)
 bp_batch(A::MatOrDict, B::AbstractMatrix, w::AbstractVector; rho::Real = 1.0, maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32,
          return_info::Bool = false) = bp_batch_call(A, B, convert(Vector{Float64}, w), rho, maxiter, tol, check_every, return_info)
+# bp for columns of B that share ONE support: min Σ_j w_j ‖X[j, :]‖₂ subject to A X = B, the row-sparse (l2,1) programme with ONE
+# stopping rule for all columns (csmp_bp_joint); one column is bp.  The weights: one per ROW of X.  Returns SparseVectors that all carry
+# the same nzind (the non-zero rows); return_info: (xs, (iterations, converged, factored, rows, resnorm)).
+function bp_joint_call(A::MatOrDict, B::AbstractMatrix, w::Vector{Float64}, rho::Real, maxiter::Int, tol::Real, check_every::Int, return_info::Bool)
+    D = dict(A)
+    BB = B isa StridedMatrix && eltype(B) <: Union{Float32,Float64} && stride(B, 1) == 1 ? B : convert(Matrix{Float64}, B)
+    size(BB, 1) == size(D, 1) || throw(DimensionMismatch("size(B, 1) = $(size(BB, 1)) but size(A, 1) = $(size(D, 1))"))
+    nsig, N = size(BB, 2), size(D, 2)
+    length(w) in (1, N) || throw(DimensionMismatch("length(w) = $(length(w)) but size(A, 2) = $N"))
+    X = zeros(Float64, N, nsig)
+    rn, it, rows, flags = zeros(Float64, max(nsig, 1)), Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0)
+    GC.@preserve BB w X rn check(D, ccall((:csmp_bp_joint, libcsmp), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Ptr{Cdouble}, Int64, Cdouble, Int64, Cdouble, Int64, Ptr{Cdouble}, Int64, Cint,
+         Ref{Int64}, Ref{Int64}, Ptr{Cdouble}, Ref{Cint}),
+        D.ctx, BB, dtype_code(eltype(BB)), max(stride(BB, 2), size(BB, 1)), nsig, CSMP_HOST, w, length(w), rho, maxiter, tol, check_every, X, max(N, 1),
+        CSMP_HOST, it, rows, rn, flags))
+    nz = findall(j -> any(!iszero, view(X, j, :)), 1:N)
+    xs = [SparseVector(N, nz, X[nz, s]) for s in 1:nsig]
+    info = (iterations = Int(it[]), converged = flags[] & CSMP_BP_CONVERGED != 0, factored = flags[] & CSMP_BP_FACTORED != 0, rows = Int(rows[]),
+            resnorm = rn[1:nsig])
+    return return_info ? (xs, info) : xs
+end
+bp_joint(A::MatOrDict, B::AbstractMatrix; rho::Real = 1.0, maxiter::Int = 16384, tol::Real = 1e-8, check_every::Int = 32, return_info::Bool = false) =
+    bp_joint_call(A, B, Float64[1.0], rho, maxiter, tol, check_every, return_info)
+bp_joint(A::MatOrDict, B::AbstractMatrix, w::Union{Real,AbstractVector}; rho::Real = 1.0, maxiter::Int = 16384, tol::Real = 1e-8,
+         check_every::Int = 32, return_info::Bool = false) =
+    bp_joint_call(A, B, w isa Real ? Float64[w] : convert(Vector{Float64}, w), rho, maxiter, tol, check_every, return_info)
 function bp_reweighted(A::MatOrDict, b::AbstractVector, scheme::Integer, ε::Real, ard_iter::Int, maxiter::Int, min_decrease::Real, rho::Real,
                        inner_maxiter::Int, tol::Real, check_every::Int, return_weights::Bool)
     D = dict(A)

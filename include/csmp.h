@@ -590,6 +590,44 @@ int csmp_bp_batch(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_
                   const double *w, int64_t nw, double rho, int64_t maxiter, double tol, int64_t check_every,
                   double *X, int64_t ldX, int x_loc, int64_t *iterations, double *resnorm, int *flags);
 
+/* bp_joint: row-sparse basis pursuit (the l2,1 "MMV" programme every joint recovery guarantee is stated for)
+ *     min sum_j w_j ||X[j, :]||_2   subject to   A X = B
+ * for columns of B that share ONE support -- csmp_bp with matrices in place of vectors; the equality-constrained companion of
+ * csmp_ista_joint and the convex counterpart of csmp_somp.  No lambda, no step size.  With Z, U of size(A,2) x nsig, P = A Z, Q = A U, E,
+ * Y of size(A,1) x nsig, t_j = w_j / rho, one iteration is
+ *     E = P - Q - B;   Y = G^-1 E  (V = R^-T E, Y = R^-1 V);   C = A' Y;   T = Z - C;
+ *     n_j = sqrt(sum_l T[j,l]^2), added by fma in column order l = 0, 1, ...;
+ *     Z+[j,:] = 0 exactly where !(n_j > t_j), else (1 - t_j / n_j) T[j,:];   U+ = T - Z+;
+ *     R = B - A Z+;   P+ = B - R;   Q+ = P - G Y - P+
+ * Start: Z = U = 0.  Every check_every iterations the host reads ||U+ - U||_F and rho ||Z+ - Z||_F and stops when both are < tol: ONE
+ * rule for all columns, so there is one iterations and one converged; reaching maxiter is not an error.  The result is Z: exactly
+ * row-sparse, every column with the same non-zero rows.
+ * B: size(A,1) x nsig, column-major, leading dimension ldB >= size(A,1), CSMP_F32 or CSMP_F64, on the host or the device (b_loc).
+ * w, nw: a host array; nw = 1 (one weight) or size(A,2) (one weight per ROW of X); non-negative and finite.
+ * X: size(A,2) x nsig doubles, leading dimension ldX >= size(A,2), on the host or the device (x_loc); rows beyond size(A,2) are not
+ * touched.  iterations, nrows (the number of non-zero rows of X), flags (CSMP_BP_CONVERGED, CSMP_BP_FACTORED as csmp_bp_batch's
+ * flags[0]): one number each, may be NULL.  resnorm (may be NULL): a host array of nsig entries, ||b_l - A z_l||_2 from the last R.
+ * nsig = 0: CSMP_OK, nothing is touched.  maxiter = 0: X = 0, iterations 0, not converged, resnorm ||b_l||.
+ * One column is csmp_bp: nsig = 1 takes csmp_bp's own solve and returns its bits.  More columns: the three M x M products read R^-1,
+ * R^-T and G once per chunk of up to eight columns; the passes for C are csmp_somp's (chunks of up to group_wide columns on the shared
+ * pass, csmp_tune group_max / group_wide apply; one sweep per column for a dictionary without a shared pass;
+ * CSMP_OPT_SCREENED_SWEEP is ignored); the residual is csmp_ista_joint's, one read of every live column of A per chunk of up to
+ * eight columns of B.
+ * Arithmetic: Float64 on the exactly promoted dictionary values, no floating-point atomics, every sum in a fixed order: the same call
+ * returns the same bits every time, whatever the chunks are, and equal columns of B give equal columns of X.  With zero weights
+ * nothing is shrunk and column s runs csmp_bp(B[:, s], w = 0)'s arithmetic bit for bit.
+ * Memory: the factor of A A' is csmp_bp's, kept by the context until csmp_set_dictionary.  The columns live in the call's own arrays,
+ * all allocated or none, released when it returns -- 8 (8 size(A,1) + 4 size(A,2)) bytes a column (size(A,1) rounded up to 256 rows)
+ * and one chunk's partial sums of the residual (128 MiB at 4096 x 65536); nsig is bounded by memory only.
+ * CSMP_EINVAL: nsig < 0, null pointers, a dtype / location that is neither, rho or tol not positive and finite, maxiter < 0,
+ * check_every < 1, a negative or non-finite weight, A A' not positive definite.  CSMP_EDIM: ldB < size(A,1), ldX < size(A,2), nw other
+ * than 1 or size(A,2), size(A,1) > size(A,2).  CSMP_ERANGE: nsig > 2^22, more than 2^19 rows.  CSMP_ESTATE: no dictionary, or a
+ * host-streamed one (as csmp_bp).  CSMP_ENOMEM: a buffer could not be allocated; no partial buffers are left behind and the context
+ * stays usable.  Everything is validated before any device work.  A refused call writes nothing. */
+int csmp_bp_joint(csmp_ctx *ctx, const void *B, int b_dtype, int64_t ldB, int64_t nsig, int b_loc,
+                  const double *w, int64_t nw, double rho, int64_t maxiter, double tol, int64_t check_every,
+                  double *X, int64_t ldX, int x_loc, int64_t *iterations, int64_t *nrows, double *resnorm, int *flags);
+
 /* bp_candes / bp_ard: basispursuit_reweighting (:18-31) with csmp_bp's solve:  x = solve(w = 1);  then for i = 2 .. outer_maxiter:  w from x
  * (scheme, eps, ard_iter: as csmp_ista_reweighted; CSMP_REWEIGHT_ARD takes supports of up to min(size(A,1), CSMP_ARD_KMAX) atoms);
  * xs = solve(w), WARM-STARTED from the z, u, p, q of the previous solve;  norm(xs - x) < min_decrease: return xs;  else x = xs.
